@@ -1,12 +1,20 @@
 """Headline benchmark: SwinIR classical x4 (48-px LQ) training patches/s on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch 32 | --per-gpu-batch B]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 A step = ModelPlain.optimize_parameters of the reference (model_plain.py:270-318): forward, L1 loss,
 backward, gradient all-reduce (N>1), Adam, EMA 0.999 — here the fused kair_amd trainer, captured in a
 HIP graph.  Inputs are seeded synthetic patches already resident in HBM.  Rank 0 prints
-ONE JSON line (plus roofline of the dominant kernel and the CPU-oracle baseline at N=1).
+ONE JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the
+result line (value, ms_per_step, the whole step's MFMA roofline from that same timing).  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  --full adds every leg that
+takes runs of its own: the in-step kernel table with the roofline of the dominant kernel, the other engines'
+lines, the PSNR parity against the CPU oracle, the other BASELINE.json configs and the CPU-oracle baseline
+(each still switched off by its --no-* option).
 """
 import argparse
 import json
@@ -469,6 +477,39 @@ def psnr_parity(net_gpu, device, dtype, n_eval=8):
             "max_abs_fp32_vs_oracle": float((E32 - Er).abs().max())}
 
 
+DUMP_CAP = 1 << 21   # elements of one dumped array (8 MiB as float32): five arrays stay well under 64 MB
+
+
+def dump_outputs(tr, loss, out_dir, seed=0):
+    """--dump-outputs: what a caller of the timed path (FusedTrainer.step) holds after the last timed step, as
+    out_dir/<name>.npy in float32 -- `loss`, the value the step returned; `E`, the network output of its forward
+    (NCHW); and the state it leaves behind, the trainer's flat buffers in parameters() order: `grads`, `params`
+    (after Adam), `ema_params`.  An array of more than DUMP_CAP elements is written as a fixed sample, its
+    elements at sorted flat indices drawn from a generator seeded with `seed` and the array's size (the same in
+    every run and every build), so two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss, "E": tr.engine.cur["E"], "grads": tr.flat_g, "params": tr.flat_p}
+    if tr.flat_e is not None:
+        arrays["ema_params"] = tr.flat_e
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        idx = dump_sample(t.numel(), DUMP_CAP, seed)
+        if idx is not None:
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
+def dump_sample(numel, cap, seed=0):
+    """Sorted flat indices (int64, `cap` of them) of the fixed sample of an array of `numel` elements, or None when
+    the array is written whole (numel <= cap)."""
+    if numel <= cap:
+        return None
+    g = torch.Generator().manual_seed(seed + numel)
+    return torch.randperm(numel, generator=g)[:cap].sort().values
+
+
 OTHER_STEPS, OTHER_WARMUP = 20, 5
 
 
@@ -579,6 +620,11 @@ def main():
     ap.add_argument("--dtype", default="fp32x3", choices=["bf16", "fp32", "fp32x3"],
                     help="fp32x3 (default): the reference's fp32 precision class on the fp16 matrix cores (split pairs); "
                          "bf16: the 16-bit engine; fp32: exact fp32 MFMA")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: kernel table and dominant-kernel roofline, the "
+                         "other engines' lines, PSNR parity, the other configs, the CPU baseline (see the --no-* options)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--drop-path", type=float, default=0.1)
@@ -694,6 +740,8 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+    if args.dump_outputs:   # before any --full leg runs the engine again
+        dump_outputs(tr, loss, args.dump_outputs)
     fl = swinir_flops(net, 48, 48)
     value = gbatch * args.steps / wall
     ms_step = 1000.0 * wall / args.steps
@@ -705,7 +753,7 @@ def main():
                  "fp32x3": "dense f16 MFMA peak / 3 (2.5 PF / 3 = 833 TF: three fp16 products per fp32 FLOP)",
                  "fp32": "dense fp32 MFMA peak (157.3 TF)"}[args.dtype]
     roles, kernels, roles_err = {}, {}, None
-    if not args.no_roles:
+    if args.full and not args.no_roles:
         try:
             roles, kernels = time_roles(tr)
         except Exception as e:  # noqa: BLE001
@@ -775,7 +823,7 @@ def main():
         # roofline: the step's dominant kernel -- the kernel (template instantiation, all its call sites) with the
         # largest summed duration in the step, as rocprofv3 ranks the bench command's kernels
         "roofline": ({**roof(kranked[0]), "kernel_ms_timing": TIMING} if kranked else
-                     {"error": roles_err or "roles skipped"}),
+                     {"error": roles_err or "kernel table not run (--full without --no-roles runs it)"}),
         "kernels_by_duration": [roof(v) for v in kranked[:10]],
         "roles_by_duration": [roof(v, k) for k, v in ranked[:12]],
         "attention_gemm_mfma": att_mfma,
@@ -788,7 +836,7 @@ def main():
         "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4),
         "final_loss": round(final_loss, 6),
     }
-    if world == 1 and not args.no_fp32_line:   # the other engines of the same program, same step
+    if args.full and world == 1 and not args.no_fp32_line:   # the other engines of the same program, same step
         for dt in ("fp32", "bf16"):
             if dt == args.dtype:
                 continue
@@ -797,14 +845,14 @@ def main():
                                                       roles=not args.no_roles)
             except Exception as e:  # noqa: BLE001
                 out[f"{dt}_engine_line"] = {"error": repr(e)}
-    if not args.no_psnr:
+    if args.full and not args.no_psnr:
         try:
             out["psnr"] = psnr_parity(net, device, args.dtype)
         except Exception as e:  # noqa: BLE001
             out["psnr"] = {"error": repr(e)}
-    if world == 1 and not args.no_other_configs:
+    if args.full and world == 1 and not args.no_other_configs:
         out["other_configs"] = other_configs(device)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
     if world > 1:

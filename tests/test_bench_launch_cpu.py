@@ -45,6 +45,22 @@ def test_gpus_n_spawns_n_ranks(n):
     assert rec["n_gpus"] == n and rec["ranks"] == list(range(n))
 
 
+def test_dump_sample_is_fixed():
+    """--dump-outputs: an array within the cap is written whole; a larger one as `cap` distinct sorted indices that
+    depend on nothing but the seed and the array's size."""
+    assert bench.dump_sample(100, 100) is None
+    a, b = bench.dump_sample(1000, 64), bench.dump_sample(1000, 64)
+    assert a.tolist() == b.tolist() == sorted(set(a.tolist())) and len(a) == 64
+    assert 0 <= int(a[0]) and int(a[-1]) < 1000
+    assert a.tolist() != bench.dump_sample(1001, 64).tolist()
+
+
+def test_full_and_dump_outputs_are_options(tmp_path):
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path / "d"), "--dry-run"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.splitlines()[-1])["dry_run"] is True
+
+
 def test_mismatch_refused():
     r = _run(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)

@@ -17,7 +17,7 @@ run_tests t_var tests/test_swinir_variants_gpu.py
 run_tests t_dist tests/test_dist_gpu.py -s
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line \
   > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 grep -h "^{" $O/bench.log | cut -c1-400
 echo done

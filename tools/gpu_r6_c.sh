@@ -13,13 +13,13 @@ run_tests() {   # $1 = log name, rest = pytest args; a test failure (rc 1) goes 
 run_tests t_range tests/test_x3_range_gpu.py -s
 run_tests t_var tests/test_swinir_variants_gpu.py -k "trainer or vs_golden"
 
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
   > $O/bench.log 2>&1 || { grep -v "^frame" $O/bench.log | tail -12; exit 1; }
 grep -h "^{" $O/bench.log | cut -c1-300
 P=$O/prof; mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o b -- \
-  python3 $R/bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
+  python3 $R/bench.py --full --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
   > $P/bench_line.txt 2> $P/bench_err.txt || { echo "stats pass failed"; tail -5 $P/bench_err.txt; exit 1; }
 find $P -name "*stats*.csv" | head
 echo done

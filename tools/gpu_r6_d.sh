@@ -14,7 +14,7 @@ run_tests t_x3 tests/test_x3_gpu.py -s
 run_tests t_range tests/test_x3_range_gpu.py
 run_tests t_var tests/test_swinir_variants_gpu.py -k "fp32x3"
 run_tests t_dist tests/test_dist_gpu.py -s -k "fp32x3"
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
   > $O/bench.log 2>&1 || { grep -v "^frame" $O/bench.log | tail -12; exit 1; }
 grep -h "^{" $O/bench.log | cut -c1-200
 echo done

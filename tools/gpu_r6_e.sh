@@ -12,7 +12,7 @@ grep -v amdgpu.ids $O/micro_b32.log
 X3_MICRO_B=4 timeout -k 10 200 python -u tools/x3_micro.py --reps 50 > $O/micro_b4.log 2>&1 || { tail -5 $O/micro_b4.log; exit 1; }
 grep -v amdgpu.ids $O/micro_b4.log
 DBGS="0 1 2 64 128" bash tools/gpu_abl.sh ${TAG:-r6e}/abl nt_ || exit 1
-timeout -k 10 300 python -u bench.py --global-batch 4 --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs \
+timeout -k 10 300 python -u bench.py --full --global-batch 4 --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs \
   --no-fp32-line --no-psnr > $O/bench_b4.log 2>&1 || { grep -v "^frame" $O/bench_b4.log | tail -12; exit 1; }
 grep -h "^{" $O/bench_b4.log | cut -c1-200
 echo done

@@ -9,7 +9,7 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc"; exit $rc; fi
 P=$O/prof; mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o b -- \
-  python3 $R/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
+  python3 $R/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-other-configs --no-fp32-line --no-psnr \
   > $P/bench_line.txt 2> $P/bench_err.txt || { echo "stats pass failed"; tail -5 $P/bench_err.txt; exit 1; }
 cd $R
 python3 - <<'PY'
@@ -22,7 +22,7 @@ for x in rows[:5]:
     print("rocprof:", x["Calls"], round(float(x["AverageNs"]) / 1e3, 2), x["Percentage"], x["Name"][:90])
 PY
 for b in 16 8 4; do
-  timeout -k 10 300 python -u bench.py --global-batch $b --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs \
+  timeout -k 10 300 python -u bench.py --full --global-batch $b --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs \
     --no-fp32-line --no-psnr > $O/bench_b$b.log 2>&1 || { grep -v "^frame" $O/bench_b$b.log | tail -12; exit 1; }
   echo "B=$b: $(grep -h '^{' $O/bench_b$b.log | cut -c1-110)"
 done
