@@ -300,7 +300,8 @@ typedef struct {
 } kair_ln_param_job;
 int kair_ln_param_reduce_grouped(const kair_ln_param_job* jobs, int njobs, void* stream);
 
-/* Fused Swin window attention (network_swinir.py:114-145) for ws=8 (64 tokens), head_dim <= 32:
+/* Fused Swin window attention (network_swinir.py:114-145) for ws=8 (64 tokens; the *_w entry points below
+ * also take ws=7, 49 tokens), head_dim <= 32:
  *   O = softmax(q*scale @ k^T + table[relidx] + shift_mask) @ v   per (window, head).
  * qkv: head-blocked [3][nWin][nh][64][32] (dtype); table: fp32 [(2ws-1)^2][nh] (reference
  * layout); O written to rows [nWin*64, ldo] window order, head h at columns h*32..h*32+31;
@@ -331,6 +332,25 @@ int kair_window_attn_bwd_ex(const void* qkv, const void* O, long ldo, const void
 int kair_window_attn_fwd_ex(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
                             long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
                             const float* mask, int mask_nw, int head_pad, void* stream);
+/* The same with the window size explicit: ws = 8 (the functions above forward here) or 7, the JPEG
+ * artifact-reduction networks' window (options/swinir/train_swinir_car_jpeg.json "window_size": 7;
+ * network_swinir.py:114-145 with window_size (7, 7)).  At ws = 7 a window has T = 49 tokens and every
+ * global layout is dense in T: q/k/v and dq/dk/dv head-blocked [3][nWin][nh][49][32], O / dO rows
+ * [nWin*49, ld], lse [nWin][nh][49], table [169][nh], mask [mask_nw][49][49], the bias-gradient
+ * partials 169 floats per (group, head).  Inside the kernels the tile keeps 64 slots; the 15 pad slots are
+ * zero-filled, take probability exactly 0 and are never stored.  ws = 7: head pad 32 and head-blocked
+ * dqkv only (dqkv_rows = 0), fp32 or bf16.  Any other ws, a shift >= ws or an H / W that is no multiple of ws
+ * is an argument error (no launch). */
+int kair_window_attn_fwd_w(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
+                           long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
+                           const float* mask, int mask_nw, int head_pad, int ws, void* stream);
+int kair_window_attn_bwd_w(const void* qkv, const void* O, long ldo, const void* dO, long lddo, int dtype,
+                           const float* table, const float* lse, void* dqkv, int dqkv_rows, float* dtable,
+                           int dtable_accumulate, float* ws, long nWin, int nh, int hd, float scale, int H, int W,
+                           int shift, const float* mask, int mask_nw, int head_pad, int win_ws, void* stream);
+/* kair_window_attn_bwd_ws for window size win_ws (partials * nh * (2 win_ws - 1)^2 floats; 0 for an
+ * unsupported size). */
+long kair_window_attn_bwd_ws_w(long nWin, int nh, int win_ws);
 
 /* Split-fp16 ("x3", KAIR_COMPUTE_X3) window attention: the fp32 reference's arithmetic on the 16-bit
  * matrix cores.  Every tensor is an fp16 pair of planes holding x 2^e (hi = f16(x 2^e), lo = f16(x 2^e -
@@ -347,6 +367,16 @@ int kair_window_attn_bwd_x3(const void* qkv, const void* qkv_lo, const void* O, 
                             const void* dO, const void* dO_lo, long lddo, const float* table, const float* lse,
                             void* dqkv, void* dqkv_lo, float* dtable, int dtable_accumulate, float* ws, long nWin,
                             int nh, int hd, float scale, int H, int W, int shift, int e_act, int e_grad, void* stream);
+/* The same with the window size explicit (8, or 7 with the 49-token layouts of kair_window_attn_fwd_w;
+ * options/swinir/train_swinir_car_jpeg.json, network_swinir.py:114-145). */
+int kair_window_attn_fwd_x3_w(const void* qkv, const void* qkv_lo, const float* table, void* O, void* O_lo, long ldo,
+                              float* lse, long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
+                              int e_in, int e_out, int ws, void* stream);
+int kair_window_attn_bwd_x3_w(const void* qkv, const void* qkv_lo, const void* O, const void* O_lo, long ldo,
+                              const void* dO, const void* dO_lo, long lddo, const float* table, const float* lse,
+                              void* dqkv, void* dqkv_lo, float* dtable, int dtable_accumulate, float* ws, long nWin,
+                              int nh, int hd, float scale, int H, int W, int shift, int e_act, int e_grad, int win_ws,
+                              void* stream);
 
 /* Deferred bias-table gradient: kair_window_attn_bwd with dtable = NULL leaves its per-group
  * partials (kair_window_attn_bwd_groups() planes of [nh][225]) in ws; one grouped launch then
@@ -356,6 +386,7 @@ long kair_window_attn_bwd_groups(long nWin, int nh, int dtype);
 typedef struct {
   const float* ws; long nWin; int nh; int dtype;
   float* dtable; int accumulate;
+  int win_ws;   /* window size of the block: 0 (= 8), 8 or 7 ([nh][169] partial planes) */
 } kair_attn_dtable_job;
 int kair_attn_dtable_grouped(const kair_attn_dtable_job* jobs, int njobs, void* stream);
 

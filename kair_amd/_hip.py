@@ -93,7 +93,8 @@ class LnParamJob(ctypes.Structure):
 
 
 class DtabJob(ctypes.Structure):
-    _fields_ = [("ws", c_vp), ("nWin", c_long), ("nh", c_int), ("dtype", c_int), ("dtable", c_vp), ("accumulate", c_int)]
+    _fields_ = [("ws", c_vp), ("nWin", c_long), ("nh", c_int), ("dtype", c_int), ("dtable", c_vp), ("accumulate", c_int),
+                ("win_ws", c_int)]
 
 
 class PackJob(ctypes.Structure):
@@ -134,6 +135,15 @@ _SIGS = {
     "kair_window_attn_fwd": [c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_long, c_int, c_int, c_float, c_int, c_int, c_int,
                              c_int, c_vp, c_int, c_vp],
     "kair_window_attn_bwd_ws": [c_long, c_int],
+    "kair_window_attn_bwd_ws_w": [c_long, c_int, c_int],
+    "kair_window_attn_fwd_w": [c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_long, c_int, c_int, c_float, c_int, c_int, c_int,
+                               c_int, c_vp, c_int, c_int, c_int, c_vp],
+    "kair_window_attn_bwd_w": [c_vp, c_vp, c_long, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_long,
+                               c_int, c_int, c_float, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
+    "kair_window_attn_fwd_x3_w": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_long, c_int, c_int, c_float, c_int, c_int,
+                                  c_int, c_int, c_int, c_int, c_int, c_vp],
+    "kair_window_attn_bwd_x3_w": [c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                  c_vp, c_long, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "kair_window_attn_bwd": [c_vp, c_vp, c_long, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_long, c_int,
                              c_int, c_float, c_int, c_int, c_int, c_vp, c_int, c_vp],
     "kair_window_attn_bwd_ex": [c_vp, c_vp, c_long, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_long,
@@ -225,7 +235,7 @@ _SIGS = {
     "kair_last_error": [],
     "kair_device_arch": [ctypes.c_char_p, c_int],
 }
-_RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_pack_table_bytes": c_long,
+_RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long}
 
@@ -352,7 +362,9 @@ def s2d(t, H, W, C, ld=None):
     return o
 
 
-def qkvblk(t, nh, hdp=32, tok=64, rowscale=None, rows_per_scale=1):
+def qkvblk(t, nh, hdp=32, tok=None, rowscale=None, rows_per_scale=1, ws=8):
+    """Head-blocked q/k/v rows [3][nWin][nh][tok][hdp]; tok defaults to the ws * ws tokens of a window."""
+    tok = ws * ws if tok is None else tok
     o = Operand()
     o._keep = (t, rowscale)
     o.ptr = ptr(t)
@@ -556,11 +568,12 @@ def row_copy(src, ld_src, M, C, copy):
     check(lib().kair_row_copy(ptr(src), ld_src, M, C, ctypes.byref(copy), stream_ptr()), "row_copy")
 
 
-def window_attn_fwd(qkv, table, O, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col=-1, mask=None, head_pad=32):
-    """head_pad: 32, or 16 (bf16, head_dim <= 16): the per-head width of the qkv / O layouts."""
+def window_attn_fwd(qkv, table, O, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col=-1, mask=None, head_pad=32, ws=8):
+    """head_pad: 32, or 16 (bf16, head_dim <= 16): the per-head width of the qkv / O layouts.
+    ws: the window size, 8 or 7 (49 tokens per window in every layout)."""
     mnw = mask.shape[0] if mask is not None else 0
-    check(lib().kair_window_attn_fwd_ex(ptr(qkv), dtype_code(qkv), ptr(table), ptr(O), ldo, ptr(lse), nWin, nh, hd, scale,
-                                        H, W, shift, ones_col, ptr(mask), mnw, head_pad, stream_ptr()), "window_attn_fwd")
+    check(lib().kair_window_attn_fwd_w(ptr(qkv), dtype_code(qkv), ptr(table), ptr(O), ldo, ptr(lse), nWin, nh, hd, scale,
+                                       H, W, shift, ones_col, ptr(mask), mnw, head_pad, ws, stream_ptr()), "window_attn_fwd")
 
 
 GROUP_MAX = 32   # jobs per kair_ln_param_reduce_grouped / kair_attn_dtable_grouped launch (LNP_MAX, DTAB_MAX)
@@ -583,25 +596,30 @@ def ln_param_reduce_grouped(jobs):
 
 
 def attn_dtable_grouped(jobs):
-    """jobs: (ws left by window_attn_bwd(dtable=None), nWin, nh, dtype code, dtable, accumulate)."""
+    """jobs: (ws left by window_attn_bwd(dtable=None), nWin, nh, dtype code, dtable, accumulate[, window size])."""
     arr = (DtabJob * len(jobs))()
-    for i, (ws, nWin, nh, dt, dtable, acc) in enumerate(jobs):
+    for i, job in enumerate(jobs):
+        ws, nWin, nh, dt, dtable, acc = job[:6]
         arr[i].ws, arr[i].nWin, arr[i].nh, arr[i].dtype = ptr(ws), nWin, nh, dt
         arr[i].dtable, arr[i].accumulate = ptr(dtable), int(acc)
+        arr[i].win_ws = job[6] if len(job) > 6 else 0
     check(lib().kair_attn_dtable_grouped(arr, len(jobs), stream_ptr()), "attn_dtable_grouped")
 
 
-def window_attn_bwd_ws(nWin, nh):
-    return lib().kair_window_attn_bwd_ws(nWin, nh)
+def window_attn_bwd_ws(nWin, nh, ws=8):
+    if ws not in (7, 8):
+        raise ValueError(f"window_attn_bwd_ws: window size {ws} (7 or 8)")
+    return lib().kair_window_attn_bwd_ws_w(nWin, nh, ws)
 
 
 def window_attn_bwd(qkv, O, ldo, dO, lddo, table, lse, dqkv, dtable, dtable_acc, ws, nWin, nh, hd, scale, H, W, shift,
-                    mask=None, dqkv_rows=False, head_pad=32):
-    """dqkv_rows: dqkv as token rows [nWin*64, 3*nh*head_pad] (bf16) instead of head-blocked."""
+                    mask=None, dqkv_rows=False, head_pad=32, win_ws=8):
+    """dqkv_rows: dqkv as token rows [nWin*64, 3*nh*head_pad] (bf16) instead of head-blocked.  win_ws: the window
+    size, 8 or 7 (`ws` is the partials workspace)."""
     mnw = mask.shape[0] if mask is not None else 0
-    check(lib().kair_window_attn_bwd_ex(ptr(qkv), ptr(O), ldo, ptr(dO), lddo, dtype_code(qkv), ptr(table), ptr(lse),
-                                        ptr(dqkv), int(dqkv_rows), ptr(dtable), int(dtable_acc), ptr(ws), nWin, nh, hd,
-                                        scale, H, W, shift, ptr(mask), mnw, head_pad, stream_ptr()), "window_attn_bwd")
+    check(lib().kair_window_attn_bwd_w(ptr(qkv), ptr(O), ldo, ptr(dO), lddo, dtype_code(qkv), ptr(table), ptr(lse),
+                                       ptr(dqkv), int(dqkv_rows), ptr(dtable), int(dtable_acc), ptr(ws), nWin, nh, hd,
+                                       scale, H, W, shift, ptr(mask), mnw, head_pad, win_ws, stream_ptr()), "window_attn_bwd")
 
 
 def _planes(t):
@@ -609,24 +627,24 @@ def _planes(t):
     return (ptr(t), None) if t.dtype == torch.float32 else (ptr(t[0]), ptr(t[1]))
 
 
-def window_attn_fwd_x3(qkv, table, O, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col=-1, e_in=0, e_out=0):
+def window_attn_fwd_x3(qkv, table, O, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col=-1, e_in=0, e_out=0, ws=8):
     """Split-fp16 window attention forward: qkv is [2, ...] fp16 (hi plane, lo plane) of x 2^e_in; O the same
     with e_out, or an fp32 tensor (natural units)."""
     o, ol = _planes(O)
-    check(lib().kair_window_attn_fwd_x3(ptr(qkv[0]), ptr(qkv[1]), ptr(table), o, ol, ldo, ptr(lse), nWin,
-                                        nh, hd, scale, H, W, shift, ones_col, e_in, e_out, stream_ptr()),
+    check(lib().kair_window_attn_fwd_x3_w(ptr(qkv[0]), ptr(qkv[1]), ptr(table), o, ol, ldo, ptr(lse), nWin,
+                                          nh, hd, scale, H, W, shift, ones_col, e_in, e_out, ws, stream_ptr()),
           "window_attn_fwd_x3")
 
 
 def window_attn_bwd_x3(qkv, O, ldo, dO, lddo, table, lse, dqkv, dtable, dtable_acc, ws, nWin, nh, hd, scale, H, W, shift,
-                       e_act=0, e_grad=0):
+                       e_act=0, e_grad=0, win_ws=8):
     """Split-fp16 window attention backward: qkv, dO are [2, ...] fp16 planes; O and dqkv (token rows [M][3 nh 32])
     fp16 pairs or fp32 (natural units); q/k/v and O pairs carry e_act, dO and a dqkv pair e_grad."""
     o, ol = _planes(O)
     dq, dql = _planes(dqkv)
-    check(lib().kair_window_attn_bwd_x3(ptr(qkv[0]), ptr(qkv[1]), o, ol, ldo, ptr(dO[0]), ptr(dO[1]), lddo,
-                                        ptr(table), ptr(lse), dq, dql, ptr(dtable), int(dtable_acc),
-                                        ptr(ws), nWin, nh, hd, scale, H, W, shift, e_act, e_grad, stream_ptr()),
+    check(lib().kair_window_attn_bwd_x3_w(ptr(qkv[0]), ptr(qkv[1]), o, ol, ldo, ptr(dO[0]), ptr(dO[1]), lddo,
+                                          ptr(table), ptr(lse), dq, dql, ptr(dtable), int(dtable_acc),
+                                          ptr(ws), nWin, nh, hd, scale, H, W, shift, e_act, e_grad, win_ws, stream_ptr()),
           "window_attn_bwd_x3")
 
 

@@ -1,7 +1,12 @@
 // Window-attention helpers shared by the bf16 / fp32 kernels (window_attn.hip) and the fp16-pair (fp32x3)
-// ("x3") kernels (attn_x3.hip): Swin window geometry (ws = 8, 64 tokens, head dim padded to 32),
+// ("x3") kernels (attn_x3.hip): Swin window geometry (window side WSZ = 8 or 7, head dim padded to 32),
 // the relative-position index and its binned gradient, the shifted-window region ids, and the
 // MFMA-fragment reads of [64][32] bf16 LDS tiles.
+//
+// The tile is always TOK = 64 slots wide (the MFMA fragment code is the same for both sizes); a window has
+// WSZ * WSZ real tokens, dense in global memory.  At WSZ = 7 the slots 49..63 are zero-filled in LDS /
+// registers, their key columns are excluded before the softmax (probability exactly 0), and their rows are
+// never stored.  Every helper takes the window side as a template parameter (default 8: the code it was).
 #pragma once
 #include "common.h"
 
@@ -17,7 +22,11 @@ KAIR_DEV void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-KAIR_DEV int relidx(int q, int k) { return ((q >> 3) - (k >> 3) + WS - 1) * (2 * WS - 1) + ((q & 7) - (k & 7) + WS - 1); }
+template <int WSZ = WS>
+KAIR_DEV int relidx(int q, int k) {
+  if constexpr (WSZ == 8) return ((q >> 3) - (k >> 3) + WS - 1) * (2 * WS - 1) + ((q & 7) - (k & 7) + WS - 1);
+  else return (q / WSZ - k / WSZ + WSZ - 1) * (2 * WSZ - 1) + (q % WSZ - k % WSZ + WSZ - 1);   // real tokens only
+}
 
 // The relative-position bias gradient of one (group, head) tile, binned inside the wave that made it:
 // out[idx] = sum of db[q][k] over the window's (query, key) pairs with relidx(q, k) = idx (the
@@ -25,9 +34,13 @@ KAIR_DEV int relidx(int q, int k) { return ((q >> 3) - (k >> 3) + WS - 1) * (2 *
 // of the 64 x 64 tile (16 KB per (group, head) at B = 4's one window per wave).  Stage 1: lane
 // (qy, ky) sums its 8 x 8 block of db along the 15 diagonals qx - kx; stage 2: lane = bin (dy, dx)
 // sums the blocks with qy - ky = dy.  Fixed order (deterministic).  scr: 1024 floats of the wave's LDS.
-constexpr int NBIN = (2 * WS - 1) * (2 * WS - 1);
-template <bool VEC>
+// WSZ = 7: 7 x 7 blocks, 13 diagonals, 169 bins; the lanes with qy = 7 or ky = 7 hold no block (zeros), and
+// the pad rows / columns 49..63 of db are never read.
+template <int WSZ> constexpr int NBIN_W = (2 * WSZ - 1) * (2 * WSZ - 1);
+constexpr int NBIN = NBIN_W<WS>;
+template <bool VEC, int WSZ = WS>
 KAIR_DEV void bin_dbias(const float* db, int ldb, float* scr, float* __restrict__ out, int lane) {
+  constexpr int WS = WSZ, NBIN = NBIN_W<WSZ>;
   const int qy = lane >> 3, ky = lane & 7;
   float d[2 * WS - 1];
 #pragma unroll
@@ -36,12 +49,16 @@ KAIR_DEV void bin_dbias(const float* db, int ldb, float* scr, float* __restrict_
   for (int qx = 0; qx < WS; ++qx) {
     const float* row = db + (qy * WS + qx) * ldb + ky * WS;
     float v[WS];
-    if constexpr (VEC) {
+    if constexpr (VEC && WSZ == 8) {
       const float4 a = *(const float4*)row, b = *(const float4*)(row + 4);
       v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     } else {
 #pragma unroll
       for (int kx = 0; kx < WS; ++kx) v[kx] = row[kx];
+      if constexpr (WSZ != 8) {   // (a lane without a block reads inside the tile and keeps zeros)
+#pragma unroll
+        for (int kx = 0; kx < WS; ++kx) v[kx] = (qy < WS && ky < WS) ? v[kx] : 0.f;
+      }
     }
 #pragma unroll
     for (int kx = 0; kx < WS; ++kx) d[qx - kx + WS - 1] += v[kx];
@@ -58,21 +75,28 @@ KAIR_DEV void bin_dbias(const float* db, int ldb, float* scr, float* __restrict_
 #pragma unroll
       for (int y = 0; y < WS; ++y) {
         const int kyy = y - dy;
-        if (kyy >= 0 && kyy < WS) s += scr[(y * WS + kyy) * 16 + j];
+        if (kyy >= 0 && kyy < WS) s += scr[(y * 8 + kyy) * 16 + j];
       }
       out[idx] = s;
     }
   }
 }
 
-KAIR_DEV int region(int coord, int n, int shift) { return coord < n - WS ? 0 : (coord < n - shift ? 1 : 2); }
+template <int WSZ = WS>
+KAIR_DEV int region(int coord, int n, int shift) { return coord < n - WSZ ? 0 : (coord < n - shift ? 1 : 2); }
 
-// region id of token t of window `wi` (index within the image) on the shifted H x W grid
+// region id of token t of window `wi` (index within the image) on the shifted H x W grid (a pad slot
+// t >= WSZ * WSZ gets some id: it is never compared for a real pair)
+template <int WSZ = WS>
 KAIR_DEV int token_region(int wi, int t, int H, int W, int shift) {
-  const int nWw = W / WS;
+  const int nWw = W / WSZ;
   const int wy = wi / nWw, wx = wi - wy * nWw;
-  return region(wy * WS + (t >> 3), H, shift) * 3 + region(wx * WS + (t & 7), W, shift);
+  if constexpr (WSZ == 8) return region(wy * WS + (t >> 3), H, shift) * 3 + region(wx * WS + (t & 7), W, shift);
+  else return region<WSZ>(wy * WSZ + t / WSZ, H, shift) * 3 + region<WSZ>(wx * WSZ + t % WSZ, W, shift);
 }
+
+// the window sides the attention kernels are instantiated for
+inline bool attn_ws_ok(int ws) { return ws == 7 || ws == 8; }
 
 typedef short __attribute__((ext_vector_type(8))) short8v;
 

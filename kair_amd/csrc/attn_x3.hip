@@ -11,6 +11,8 @@
 // product 2^-8).  The fp32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the 16-bit rate; three 16-bit
 // products cost 3/16.
 //
+// Window side 8 or 7 (template parameter WSZ; 7: 49 real tokens in the 64-slot tile, attn_common.h -- every "64"
+// of the global layouts below reads 49).
 // Layouts as the bf16 kernels (window_attn.hip): q/k/v head-blocked [3][nWin][nh][64][32], O and dO
 // token rows (window order, head h at columns h*32..), lse [nWin][nh][64]; each fp16 tensor has its lo
 // plane in a second buffer of the same layout.  The backward writes dq/dk/dv as token rows
@@ -59,12 +61,14 @@ KAIR_DEV void pair4(const float (&v)[4], float sc, f16x4& hi, f16x4& lo) {
 // S^T = K Q^T operands), v hi / lo planes staged in LDS for the transposed P.V fragments; O^T = V^T P^T
 // (lane = query) stored 8 bytes per plane per register group.
 // ------------------------------------------------------------------------------------------
+template <int WSZ>
 __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* __restrict__ qkv, const f16* __restrict__ qkvl,
                                                                   const float* __restrict__ table, f16* __restrict__ O,
                                                                   f16* __restrict__ Ol, long ldo, float* __restrict__ lse,
                                                                   long nWin, int nh, float scale, int H, int W, int shift,
                                                                   int ones_col, int e_in, int e_out) {
   constexpr int LD = ATT_LD, NW = FWD_NW;
+  constexpr int TT = WSZ * WSZ, NBIN = NBIN_W<WSZ>;   // real tokens of a window; bias-table rows
   __shared__ __attribute__((aligned(16))) f16 sV[NW][2][TOK * LD];
   __shared__ float sTab[NW][232];
   __shared__ int sReg[NW][TOK];
@@ -73,8 +77,8 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
   if (task >= nWin * nh) return;
   const long win = task / nh;
   const int h = (int)(task - win * nh);
-  const long M = nWin * TOK;
-  const long blk = (win * nh + h) * TOK * HDP;
+  const long M = nWin * TT;
+  const long blk = (win * nh + h) * TT * HDP;
   const long part = M * nh * HDP;
   const int l31 = lane & 31, hh = lane >> 5;
   f16x8 Qh[2][2], Ql[2][2], Kh[2][2], Kl[2][2];
@@ -83,17 +87,24 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const long o = blk + (long)(t * 32 + l31) * HDP + 16 * s + 8 * hh;
-      Qh[t][s] = *(const f16x8*)(qkv + o);
-      Ql[t][s] = *(const f16x8*)(qkvl + o);
-      Kh[t][s] = *(const f16x8*)(qkv + part + o);
-      Kl[t][s] = *(const f16x8*)(qkvl + part + o);
       const int lo = (t * 32 + l31) * LD + 16 * s + 8 * hh;
-      *(f16x8*)(sV[w][0] + lo) = *(const f16x8*)(qkv + 2 * part + o);
-      *(f16x8*)(sV[w][1] + lo) = *(const f16x8*)(qkvl + 2 * part + o);
+      if (TT == TOK || t * 32 + l31 < TT) {
+        Qh[t][s] = *(const f16x8*)(qkv + o);
+        Ql[t][s] = *(const f16x8*)(qkvl + o);
+        Kh[t][s] = *(const f16x8*)(qkv + part + o);
+        Kl[t][s] = *(const f16x8*)(qkvl + part + o);
+        *(f16x8*)(sV[w][0] + lo) = *(const f16x8*)(qkv + 2 * part + o);
+        *(f16x8*)(sV[w][1] + lo) = *(const f16x8*)(qkvl + 2 * part + o);
+      } else {   // a pad slot: zero q / k / v
+        const f16x8 z = {};
+        Qh[t][s] = z; Ql[t][s] = z; Kh[t][s] = z; Kl[t][s] = z;
+        *(f16x8*)(sV[w][0] + lo) = z;
+        *(f16x8*)(sV[w][1] + lo) = z;
+      }
     }
   for (int i = lane; i < NBIN; i += 64) sTab[w][i] = table[i * nh + h];
-  const int nW = (H / WS) * (W / WS);
-  sReg[w][lane] = shift > 0 ? token_region((int)(win % nW), lane, H, W, shift) : 0;
+  const int nW = (H / WSZ) * (W / WSZ);
+  sReg[w][lane] = shift > 0 ? token_region<WSZ>((int)(win % nW), lane, H, W, shift) : 0;
 
   // S^T = K Q^T : tiles [kt][qt], lane column = query, registers = keys
   f32x16 acc[2][2];
@@ -126,8 +137,16 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ki = kt * 32 + acc_row(r, hh);
-        float sc = acc[kt][qt][r] * sqk + sTab[w][relidx(qi, ki)];
-        if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
+        float sc;
+        if constexpr (TT == TOK) {
+          sc = acc[kt][qt][r] * sqk + sTab[w][relidx(qi, ki)];
+          if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
+        } else {   // pad slots: no table entry; a pad key leaves the softmax (exp(-3e38 - mx) is exactly 0)
+          const bool real = qi < TT && ki < TT;
+          sc = acc[kt][qt][r] * sqk + (real ? sTab[w][relidx<WSZ>(qi, ki)] : 0.f);
+          if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
+          if (ki >= TT) sc = -3.0e38f;
+        }
         acc[kt][qt][r] = sc;
         mx = fmaxf(mx, sc);
       }
@@ -147,7 +166,7 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[kt][qt][r] *= inv;
-    if (hh == 0) lse[task * TOK + qi] = mx + __logf(sum);
+    if (hh == 0 && (TT == TOK || qi < TT)) lse[task * TT + qi] = mx + __logf(sum);
   }
   // O^T = V^T P^T : tile [qt] rows = d, lane = query (P with exponent P_EXP)
   const float so = ldexpf(1.f, e_out - e_in - P_EXP), sone = ldexpf(1.f, e_out), sp = ldexpf(1.f, P_EXP);
@@ -169,7 +188,8 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
         o = mfma32(vl, ph, o);
       }
     const int qi = qt * 32 + l31;
-    const long orow = (win * TOK + qi) * ldo + h * HDP;
+    const long orow = (win * TT + qi) * ldo + h * HDP;
+    if (TT != TOK && qi >= TT) continue;   // a pad query row is never stored
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int d0 = 8 * g + 4 * hh;
@@ -199,6 +219,7 @@ __global__ __launch_bounds__(64 * FWD_NW, 3) void attn_fwd_x3_kernel(const f16* 
 // P is recomputed from q, k and the saved log-sum-exp.
 // ------------------------------------------------------------------------------------------
 constexpr int BWD_NW = 2;
+template <int WSZ>
 __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* __restrict__ qkv, const f16* __restrict__ qkvl,
                                                             const f16* __restrict__ O, const f16* __restrict__ Ol, long ldo,
                                                             const f16* __restrict__ dO, const f16* __restrict__ dOl, long lddo,
@@ -207,6 +228,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
                                                             float* __restrict__ dB_part, long nWin, int nh, int wpg,
                                                             float scale, int H, int W, int shift, int e_act, int e_grad) {
   constexpr int LD = ATT_LD, LDB = 72;
+  constexpr int TT = WSZ * WSZ, NBIN = NBIN_W<WSZ>;   // real tokens of a window; bias-table rows
   // plane p (0 hi, 1 lo): [q | dO] tiles [64][LD]; after dV / dK wave w's dS tile [q][its 32 keys] at w * TOK * LD
   __shared__ __attribute__((aligned(16))) f16 sQG[2][2 * TOK * LD];
   // [wave][plane]: the wave's k rows [32][LD]; after its dQ MFMAs, its exchange slot (16 floats per lane)
@@ -224,11 +246,11 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
   if (gtask >= ngroups * nh) return;
   const int h = (int)(gtask % nh);
   const long grp = gtask / nh;
-  const long M = nWin * TOK;
+  const long M = nWin * TT;
   const long part = M * nh * HDP;
   const int l31 = lane & 31, hh = lane >> 5;
   for (int i = tid; i < NBIN; i += 64 * BWD_NW) sTab[i] = table[i * nh + h];
-  const int nW = (H / WS) * (W / WS);
+  const int nW = (H / WSZ) * (W / WSZ);
   const long tstr = 3L * nh * HDP;
   // exponents: q/k/v and O carry e_act, dO / dS / dq,dk,dv carry e_grad; everything below is rescaled
   // to natural units (S, dP, delta, P, dS) before it is combined
@@ -243,7 +265,15 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
   // fragment f[s] of token t * 32 + l31 (8 consecutive d at 16 s + 8 hh) and its LDS image (row r0 + l31)
   auto ldfrag = [&](const f16* g, long ld, int t, f16x8 (&f)[2]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) f[s] = *(const f16x8*)(g + (long)(t * 32 + l31) * ld + 16 * s + 8 * hh);
+    for (int s = 0; s < 2; ++s) {
+      if constexpr (TT == TOK) {
+        f[s] = *(const f16x8*)(g + (long)(t * 32 + l31) * ld + 16 * s + 8 * hh);
+      } else {   // a pad slot's row does not exist in global memory: zeros
+        const f16x8 z = {};
+        f[s] = z;
+        if (t * 32 + l31 < TT) f[s] = *(const f16x8*)(g + (long)(t * 32 + l31) * ld + 16 * s + 8 * hh);
+      }
+    }
   };
   auto stfrag = [&](f16* tile, int r0, const f16x8 (&f)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -261,7 +291,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
   if (w1 > nWin) w1 = nWin;
   const int ki = w * 32 + l31;   // this lane's key
   for (long win = w0; win < w1; ++win) {
-    const long blk = (win * nh + h) * TOK * HDP;
+    const long blk = (win * nh + h) * TT * HDP;
     __syncthreads();   // the previous window's tiles and exchange slots are no longer read
     f32x16 S[2], dP[2];
 #pragma unroll
@@ -294,8 +324,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
       f16x8 Fgh[2][2], Fgl[2][2], Fvh[2], Fvl[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        ldfrag(dO + win * TOK * lddo + h * HDP, lddo, t, Fgh[t]);
-        ldfrag(dOl + win * TOK * lddo + h * HDP, lddo, t, Fgl[t]);
+        ldfrag(dO + win * TT * lddo + h * HDP, lddo, t, Fgh[t]);
+        ldfrag(dOl + win * TT * lddo + h * HDP, lddo, t, Fgl[t]);
       }
       ldfrag(qkv + 2 * part + blk, HDP, w, Fvh);
       ldfrag(qkvl + 2 * part + blk, HDP, w, Fvl);
@@ -304,8 +334,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
       float dsum = 0.f;
       if (Ol) {
         f16x8 Foh[2], Fol[2];
-        ldfrag(O + win * TOK * ldo + h * HDP, ldo, w, Foh);
-        ldfrag(Ol + win * TOK * ldo + h * HDP, ldo, w, Fol);
+        ldfrag(O + win * TT * ldo + h * HDP, ldo, w, Foh);
+        ldfrag(Ol + win * TT * ldo + h * HDP, ldo, w, Fol);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const f16x8 gh = w ? Fgh[1][s] : Fgh[0][s], gl = w ? Fgl[1][s] : Fgl[0][s];
@@ -313,11 +343,12 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
           for (int j = 0; j < 8; ++j) dsum += ((float)gh[j] + (float)gl[j]) * ((float)Foh[s][j] + (float)Fol[s][j]) * s_o;
         }
       } else {   // fp32 O (natural units)
-        const float* Of = (const float*)O + win * TOK * ldo + h * HDP;
+        const float* Of = (const float*)O + win * TT * ldo + h * HDP;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const float* op = Of + (long)(w * 32 + l31) * ldo + 16 * s + 8 * hh;
-          const float4 a = *(const float4*)op, b = *(const float4*)(op + 4);
+          float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+          if (TT == TOK || w * 32 + l31 < TT) { a = *(const float4*)op; b = *(const float4*)(op + 4); }
           const float ov[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
           const f16x8 gh = w ? Fgh[1][s] : Fgh[0][s], gl = w ? Fgl[1][s] : Fgl[0][s];
 #pragma unroll
@@ -326,7 +357,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
       }
       dsum += __shfl_xor(dsum, 32, 64);
       if (hh == 0) {
-        sRow[0][w * 32 + l31] = lse[(win * nh + h) * TOK + w * 32 + l31];
+        // (a pad query: lse 0, delta 0 -- finite row terms; its P is forced to 0 below)
+        sRow[0][w * 32 + l31] = (TT == TOK || w * 32 + l31 < TT) ? lse[(win * nh + h) * TT + w * 32 + l31] : 0.f;
         sRow[1][w * 32 + l31] = dsum * s_g;
       }
 #pragma unroll
@@ -338,21 +370,22 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
           dP[qt] = mfma32(Fgl[qt][s], Fvh[s], dP[qt]);
         }
     }
-    if (w == 0) sReg[lane] = shift > 0 ? token_region((int)(win % nW), lane, H, W, shift) : 0;
+    if (w == 0) sReg[lane] = shift > 0 ? token_region<WSZ>((int)(win % nW), lane, H, W, shift) : 0;
     __syncthreads();   // the q / dO tiles, lse / delta and the token regions of both halves
 
     // P = exp(S*scale + bias + mask - lse) ; dS = P (dP - delta), natural units.  Lane = key ki, register r
     // of tile qt = query 32 qt + 8 (r/4) + r%4 + 4 hh: every LDS operand at a compile-time offset from a
     // per-lane base (the bf16 kernel's indexing).
-    const int wi_img = (int)(win % nW), nWw = W / WS;
-    const bool mixed = shift > 0 && ((wi_img / nWw) == H / WS - 1 || (wi_img % nWw) == nWw - 1);
+    const int wi_img = (int)(win % nW), nWw = W / WSZ;
+    const bool mixed = shift > 0 && ((wi_img / nWw) == H / WSZ - 1 || (wi_img % nWw) == nWw - 1);
     const float* rl = &sRow[0][4 * hh];
     const float* rd = &sRow[1][4 * hh];
     const int* rg = &sReg[4 * hh];
     const float sqk = scale * s_qk;
     {
       const int rk = sReg[ki];
-      const float* tb = &sTab[15 * (WS - 1 - (ki >> 3)) + (WS - 1 - (ki & 7)) + 4 * hh];
+      const float* tb = nullptr;   // WSZ = 8: the compile-time-offset table base
+      if constexpr (TT == TOK) tb = &sTab[15 * (WS - 1 - (ki >> 3)) + (WS - 1 - (ki & 7)) + 4 * hh];
       float* dbl = sDB + 4 * hh * LDB + ki;
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
@@ -362,7 +395,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             const int r = r0 + u, o = 32 * qt + 8 * (r >> 2) + (r & 3);
-            tv[u] = tb[15 * (4 * qt + (r >> 2)) + (r & 3)];
+            if constexpr (TT == TOK) tv[u] = tb[15 * (4 * qt + (r >> 2)) + (r & 3)];
+            else tv[u] = (o + 4 * hh < TT && ki < TT) ? sTab[relidx<WSZ>(o + 4 * hh, ki)] : 0.f;
             lv[u] = rl[o];
             dv[u] = rd[o];
             bv[u] = dbl[o * LDB];
@@ -375,7 +409,11 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             const int r = r0 + u;
-            const float p = __expf(fmaf(S[qt][r], sqk, tv[u]) - lv[u]);
+            float p = __expf(fmaf(S[qt][r], sqk, tv[u]) - lv[u]);
+            if constexpr (TT != TOK) {   // a pad query or key: P = 0 exactly, so dS = 0 * (0 - 0) = 0
+              const int qi = 32 * qt + 8 * (r >> 2) + (r & 3) + 4 * hh;
+              if (qi >= TT || ki >= TT) p = 0.f;
+            }
             S[qt][r] = p;
             const float d = p * (dP[qt][r] * s_dp - dv[u]);
             dP[qt][r] = d;
@@ -387,9 +425,9 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
     }
     // dV^T = dO^T P and dK^T = scale * Q^T dS of the wave's keys: rows = d, lane = key; token-row outputs
     // carrying e_grad (dS enters as the pair of dS 2^e_grad)
-    f16* dq_out = dqkv + win * TOK * tstr + h * HDP;
-    f16* dql_out = dqkvl ? dqkvl + win * TOK * tstr + h * HDP : nullptr;
-    float* dqf = (float*)dqkv + win * TOK * tstr + h * HDP;
+    f16* dq_out = dqkv + win * TT * tstr + h * HDP;
+    f16* dql_out = dqkvl ? dqkvl + win * TT * tstr + h * HDP : nullptr;
+    float* dqf = (float*)dqkv + win * TT * tstr + h * HDP;
     const long koff = (long)nh * HDP, voff = 2L * nh * HDP;
     {
       f32x16 av, ak;
@@ -414,6 +452,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
         }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
+        if (TT != TOK && ki >= TT) break;   // a pad key row is never stored
         float va[4], ka[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -477,6 +516,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
       const long qi = w * 32 + l31;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
+        if (TT != TOK && qi >= TT) break;   // a pad query row is never stored
         float qa[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) qa[j] = (aqk[4 * g + j] + xi[(4 * g + j) * 64 + lane]) * (scale * s_dk);
@@ -493,7 +533,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attn_bwd_x3_kernel(const f16* 
   }
   // partial bias gradient of this (group, head), binned by wave 0 (its k tile is free scratch now)
   __syncthreads();
-  if (w == 0) bin_dbias<true>(sDB, LDB, (float*)&sK[0][0][0], dB_part + (grp * nh + h) * NBIN, lane);
+  if (w == 0) bin_dbias<true, WSZ>(sDB, LDB, (float*)&sK[0][0][0], dB_part + (grp * nh + h) * NBIN, lane);
 }
 
 int g_x3_cus = 0;
@@ -520,13 +560,14 @@ long kair_attn_x3_wpg(long nWin, int nh) {
   return w < 1 ? 1 : w;
 }
 
-extern "C" int kair_window_attn_fwd_x3(const void* qkv, const void* qkv_lo, const float* table, void* O, void* O_lo, long ldo,
-                                       float* lse, long nWin, int nh, int hd, float scale, int H, int W, int shift,
-                                       int ones_col, int e_in, int e_out, void* stream) {
+extern "C" int kair_window_attn_fwd_x3_w(const void* qkv, const void* qkv_lo, const float* table, void* O, void* O_lo, long ldo,
+                                         float* lse, long nWin, int nh, int hd, float scale, int H, int W, int shift,
+                                         int ones_col, int e_in, int e_out, int ws, void* stream) {
+  KAIR_CHECK_ARG(attn_ws_ok(ws), "window_attn_fwd_x3: window size %d (7 or 8)", ws);
   KAIR_CHECK_ARG(qkv && qkv_lo && table && O && lse, "window_attn_fwd_x3: null pointer");
   KAIR_CHECK_ARG(hd > 0 && hd <= HDP && nh > 0 && nWin > 0, "window_attn_fwd_x3: head_dim %d must be <= 32", hd);
-  KAIR_CHECK_ARG(H % WS == 0 && W % WS == 0 && (shift == 0 || (shift > 0 && shift < WS)),
-                 "window_attn_fwd_x3: grid %dx%d / shift %d", H, W, shift);
+  KAIR_CHECK_ARG(H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && (shift == 0 || (shift > 0 && shift < ws)),
+                 "window_attn_fwd_x3: grid %dx%d / shift %d at window size %d", H, W, shift, ws);
   KAIR_CHECK_ARG(ldo >= nh * HDP && ldo % 8 == 0, "window_attn_fwd_x3: ldo");
   KAIR_CHECK_ARG(ones_col < 0 || (ones_col < nh * HDP && ones_col % HDP >= hd), "window_attn_fwd_x3: ones column must be a pad column");
   KAIR_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)qkv_lo % 16) == 0 && ((uintptr_t)O % (O_lo ? 8 : 16)) == 0 &&
@@ -535,11 +576,51 @@ extern "C" int kair_window_attn_fwd_x3(const void* qkv, const void* qkv_lo, cons
   const long tasks = nWin * nh;
   const long nb = (tasks + FWD_NW - 1) / FWD_NW;
   KAIR_CHECK_ARG(e_in > -60 && e_in < 60 && e_out > -60 && e_out < 60, "window_attn_fwd_x3: exponents");
-  KAIR_LAUNCH(attn_fwd_x3_kernel, dim3((unsigned)nb), dim3(64 * FWD_NW), 0, (hipStream_t)stream, (const f16*)qkv,
+  if (ws == 7)
+    KAIR_LAUNCH(attn_fwd_x3_kernel<7>, dim3((unsigned)nb), dim3(64 * FWD_NW), 0, (hipStream_t)stream, (const f16*)qkv,
+                (const f16*)qkv_lo, table, (f16*)O, (f16*)O_lo, ldo, lse, nWin, nh, scale, H, W, shift, ones_col, e_in, e_out);
+  else
+    KAIR_LAUNCH(attn_fwd_x3_kernel<8>, dim3((unsigned)nb), dim3(64 * FWD_NW), 0, (hipStream_t)stream, (const f16*)qkv,
                      (const f16*)qkv_lo, table, (f16*)O, (f16*)O_lo, ldo, lse, nWin, nh, scale, H, W, shift, ones_col, e_in,
                      e_out);
   KAIR_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int kair_window_attn_fwd_x3(const void* qkv, const void* qkv_lo, const float* table, void* O, void* O_lo, long ldo,
+                                       float* lse, long nWin, int nh, int hd, float scale, int H, int W, int shift,
+                                       int ones_col, int e_in, int e_out, void* stream) {
+  return kair_window_attn_fwd_x3_w(qkv, qkv_lo, table, O, O_lo, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col, e_in,
+                                   e_out, WS, stream);
+}
+
+extern "C" int kair_window_attn_bwd_x3_w(const void* qkv, const void* qkv_lo, const void* O, const void* O_lo, long ldo,
+                                         const void* dO, const void* dO_lo, long lddo, const float* table, const float* lse,
+                                         void* dqkv, void* dqkv_lo, float* dtable, int dtable_accumulate, float* ws, long nWin,
+                                         int nh, int hd, float scale, int H, int W, int shift, int e_act, int e_grad,
+                                         int win_ws, void* stream) {
+  KAIR_CHECK_ARG(attn_ws_ok(win_ws), "window_attn_bwd_x3: window size %d (7 or 8)", win_ws);
+  KAIR_CHECK_ARG(qkv && qkv_lo && O && dO && dO_lo && table && lse && dqkv && ws, "window_attn_bwd_x3: null pointer");
+  KAIR_CHECK_ARG((O_lo || (uintptr_t)O % 16 == 0) && (dqkv_lo || (uintptr_t)dqkv % 16 == 0), "window_attn_bwd_x3: alignment");
+  KAIR_CHECK_ARG(hd > 0 && hd <= HDP && nh > 0 && nWin > 0, "window_attn_bwd_x3: head_dim");
+  KAIR_CHECK_ARG(H > 0 && W > 0 && H % win_ws == 0 && W % win_ws == 0 && (shift == 0 || (shift > 0 && shift < win_ws)),
+                 "window_attn_bwd_x3: grid %dx%d / shift %d at window size %d", H, W, shift, win_ws);
+  KAIR_CHECK_ARG(ldo % 8 == 0 && lddo % 8 == 0, "window_attn_bwd_x3: strides");
+  const long wpg = kair_attn_x3_wpg(nWin, nh);
+  const long ngroups = (nWin + wpg - 1) / wpg;
+  hipStream_t s = (hipStream_t)stream;
+  KAIR_CHECK_ARG(e_act > -60 && e_act < 60 && e_grad > -60 && e_grad < 60, "window_attn_bwd_x3: exponents");
+  if (win_ws == 7)
+    KAIR_LAUNCH(attn_bwd_x3_kernel<7>, dim3((unsigned)(ngroups * nh)), dim3(64 * BWD_NW), 0, s, (const f16*)qkv,
+                (const f16*)qkv_lo, (const f16*)O, (const f16*)O_lo, ldo, (const f16*)dO, (const f16*)dO_lo, lddo, table, lse,
+                (f16*)dqkv, (f16*)dqkv_lo, ws, nWin, nh, (int)wpg, scale, H, W, shift, e_act, e_grad);
+  else
+    KAIR_LAUNCH(attn_bwd_x3_kernel<8>, dim3((unsigned)(ngroups * nh)), dim3(64 * BWD_NW), 0, s, (const f16*)qkv, (const f16*)qkv_lo,
+                     (const f16*)O, (const f16*)O_lo, ldo, (const f16*)dO, (const f16*)dO_lo, lddo, table, lse, (f16*)dqkv,
+                     (f16*)dqkv_lo, ws, nWin, nh, (int)wpg, scale, H, W, shift, e_act, e_grad);
+  KAIR_CHECK_LAUNCH();
+  if (!dtable) return 0;   // deferred: the per-group partials stay in ws for kair_attn_dtable_grouped (dtype x3)
+  return kair_attn_dtable_sum(ws, ngroups, nh, dtable, dtable_accumulate, s, win_ws);
 }
 
 extern "C" int kair_window_attn_bwd_x3(const void* qkv, const void* qkv_lo, const void* O, const void* O_lo, long ldo,
@@ -547,20 +628,6 @@ extern "C" int kair_window_attn_bwd_x3(const void* qkv, const void* qkv_lo, cons
                                        void* dqkv, void* dqkv_lo, float* dtable, int dtable_accumulate, float* ws, long nWin,
                                        int nh, int hd, float scale, int H, int W, int shift, int e_act, int e_grad,
                                        void* stream) {
-  KAIR_CHECK_ARG(qkv && qkv_lo && O && dO && dO_lo && table && lse && dqkv && ws, "window_attn_bwd_x3: null pointer");
-  KAIR_CHECK_ARG((O_lo || (uintptr_t)O % 16 == 0) && (dqkv_lo || (uintptr_t)dqkv % 16 == 0), "window_attn_bwd_x3: alignment");
-  KAIR_CHECK_ARG(hd > 0 && hd <= HDP && nh > 0 && nWin > 0, "window_attn_bwd_x3: head_dim");
-  KAIR_CHECK_ARG(H % WS == 0 && W % WS == 0 && (shift == 0 || (shift > 0 && shift < WS)), "window_attn_bwd_x3: geometry");
-  KAIR_CHECK_ARG(ldo % 8 == 0 && lddo % 8 == 0, "window_attn_bwd_x3: strides");
-  const long wpg = kair_attn_x3_wpg(nWin, nh);
-  const long ngroups = (nWin + wpg - 1) / wpg;
-  hipStream_t s = (hipStream_t)stream;
-  KAIR_CHECK_ARG(e_act > -60 && e_act < 60 && e_grad > -60 && e_grad < 60, "window_attn_bwd_x3: exponents");
-  KAIR_LAUNCH(attn_bwd_x3_kernel, dim3((unsigned)(ngroups * nh)), dim3(64 * BWD_NW), 0, s, (const f16*)qkv, (const f16*)qkv_lo,
-                     (const f16*)O, (const f16*)O_lo, ldo, (const f16*)dO, (const f16*)dO_lo, lddo, table, lse, (f16*)dqkv,
-                     (f16*)dqkv_lo, ws, nWin, nh, (int)wpg, scale, H, W, shift, e_act, e_grad);
-  KAIR_CHECK_LAUNCH();
-  if (!dtable) return 0;   // deferred: the per-group partials stay in ws for kair_attn_dtable_grouped (dtype x3)
-  kair_attn_dtable_sum(ws, ngroups, nh, dtable, dtable_accumulate, s);
-  return 0;
+  return kair_window_attn_bwd_x3_w(qkv, qkv_lo, O, O_lo, ldo, dO, dO_lo, lddo, table, lse, dqkv, dqkv_lo, dtable,
+                                   dtable_accumulate, ws, nWin, nh, hd, scale, H, W, shift, e_act, e_grad, WS, stream);
 }

@@ -361,7 +361,7 @@ int kair_launch_finalize_grouped(const FinGroup& g, hipStream_t s);
 // fp16-pair (fp32x3) window attention (attn_x3.hip): windows per backward wave, and the bias-table partial sum
 // shared with window_attn.hip
 long kair_attn_x3_wpg(long nWin, int nh);
-int kair_attn_dtable_sum(const float* ws, long ngroups, int nh, float* dtable, int accumulate, hipStream_t s);
+int kair_attn_dtable_sum(const float* ws, long ngroups, int nh, float* dtable, int accumulate, hipStream_t s, int win_ws = 8);
 
 // split-fp16 GEMMs (gemm_x3.hip), reached through kair_gemm_nt / kair_gemm_tn with compute KAIR_COMPUTE_X3,
 // and the operand validation they share with gemm.hip

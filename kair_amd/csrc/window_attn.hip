@@ -1,6 +1,7 @@
 // Fused Swin window attention for gfx950 (network_swinir.py:114-145, WindowAttention.forward):
 //   S = (q*scale) k^T + table[relative_position_index] (+ shifted-window region mask, -100)
-//   P = softmax(S) ; O = P v          per (window, head), window 8x8 = 64 tokens, head_dim <= 32
+//   P = softmax(S) ; O = P v          per (window, head), window 8x8 = 64 tokens (or 7x7 = 49 tokens in
+//                                       the same 64-slot tile, attn_common.h), head_dim <= 32
 // and its backward (dq, dk, dv, d table), flash-style: P is recomputed from q, k and the saved
 // row log-sum-exp, nothing of size 64x64 per (window, head) touches HBM.
 //
@@ -26,8 +27,8 @@ template <bool BF> struct AT {
 };
 
 // stage a [64][32] tile (element type T in global, contiguous rows of `ld` elements starting at
-// column c0) into LDS with row stride LD
-template <bool BF>
+// column c0) into LDS with row stride LD; only the first TT rows exist in global memory, the rest are zero-filled
+template <bool BF, int TT = TOK>
 KAIR_DEV void stage_tile(typename AT<BF>::T* lds, const typename AT<BF>::T* g, long ld, int lane) {
   using T = typename AT<BF>::T;
   constexpr int LD = AT<BF>::LD;
@@ -38,9 +39,16 @@ KAIR_DEV void stage_tile(typename AT<BF>::T* lds, const typename AT<BF>::T* g, l
     const int c = lane + 64 * i;
     const int row = c / CPR, col = (c % CPR) * EPC;
     if constexpr (BF) {
-      *(bf16x8*)(lds + row * LD + col) = *(const bf16x8*)(g + row * ld + col);
+      if constexpr (TT == TOK) {
+        *(bf16x8*)(lds + row * LD + col) = *(const bf16x8*)(g + row * ld + col);
+      } else {
+        bf16x8 v = {};
+        if (row < TT) v = *(const bf16x8*)(g + row * ld + col);
+        *(bf16x8*)(lds + row * LD + col) = v;
+      }
     } else {
-      const float4 v = *(const float4*)(g + row * ld + col);
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (TT == TOK || row < TT) v = *(const float4*)(g + row * ld + col);
       float* d = (float*)lds + row * LD + col;
       d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
     }
@@ -51,7 +59,7 @@ KAIR_DEV void stage_tile(typename AT<BF>::T* lds, const typename AT<BF>::T* g, l
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-template <bool BF>
+template <bool BF, int WSZ = WS>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T* __restrict__ qkv,
                                                        const float* __restrict__ table, typename AT<BF>::T* __restrict__ O,
                                                        long ldo, float* __restrict__ lse, long nWin, int nh, float scale,
@@ -60,6 +68,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T*
   using T = typename AT<BF>::T;
   constexpr int LD = AT<BF>::LD;
   constexpr int WAVES = NWAVES<BF>;
+  constexpr int TT = WSZ * WSZ;   // real tokens of a window (global layouts are dense in TT; the tile has TOK slots)
   __shared__ __attribute__((aligned(16))) T sQ[WAVES][TOK * LD];
   __shared__ __attribute__((aligned(16))) T sK[WAVES][TOK * LD];
   __shared__ __attribute__((aligned(16))) T sV[WAVES][TOK * LD];
@@ -70,17 +79,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T*
   if (task >= nWin * nh) return;
   const long win = task / nh;
   const int h = (int)(task - win * nh);
-  const long M = nWin * TOK;
-  const long blk = (win * nh + h) * TOK * HDP;
+  const long M = nWin * TT;
+  const long blk = (win * nh + h) * TT * HDP;
   const long part = M * nh * HDP;
   T* q = sQ[w]; T* k = sK[w]; T* v = sV[w];
-  stage_tile<BF>(q, qkv + blk, HDP, lane);
-  stage_tile<BF>(k, qkv + part + blk, HDP, lane);
-  stage_tile<BF>(v, qkv + 2 * part + blk, HDP, lane);
-  for (int i = lane; i < (2 * WS - 1) * (2 * WS - 1); i += 64) sTab[w][i] = table[i * nh + h];
-  const int nW = (H / WS) * (W / WS);
+  stage_tile<BF, TT>(q, qkv + blk, HDP, lane);
+  stage_tile<BF, TT>(k, qkv + part + blk, HDP, lane);
+  stage_tile<BF, TT>(v, qkv + 2 * part + blk, HDP, lane);
+  for (int i = lane; i < NBIN_W<WSZ>; i += 64) sTab[w][i] = table[i * nh + h];
+  const int nW = (H / WSZ) * (W / WSZ);
   const int wi = (int)(win % nW);
-  sReg[w][lane] = shift > 0 ? token_region(wi, lane, H, W, shift) : 0;
+  sReg[w][lane] = shift > 0 ? token_region<WSZ>(wi, lane, H, W, shift) : 0;
   wave_sync();
 
   // S^T = K Q^T : tiles [kt][qt], lane column = query, registers = keys
@@ -134,9 +143,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T*
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ki = kt * 32 + acc_row(r, hh);
-        float sc = acc[kt][qt][r] * scale + sTab[w][relidx(qi, ki)];
-        if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
-        if (amask) sc += amask[((win % mask_nw) * TOK + qi) * TOK + ki];
+        float sc;
+        if constexpr (TT == TOK) {
+          sc = acc[kt][qt][r] * scale + sTab[w][relidx(qi, ki)];
+          if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
+          if (amask) sc += amask[((win % mask_nw) * TOK + qi) * TOK + ki];
+        } else {   // pad slots: no table entry; a pad key leaves the softmax (exp(-3e38 - mx) is exactly 0)
+          const bool real = qi < TT && ki < TT;
+          sc = acc[kt][qt][r] * scale + (real ? sTab[w][relidx<WSZ>(qi, ki)] : 0.f);
+          if (shift > 0 && sReg[w][ki] != rq) sc += -100.f;
+          if (amask && real) sc += amask[((win % mask_nw) * TT + qi) * TT + ki];
+          if (ki >= TT) sc = -3.0e38f;
+        }
         acc[kt][qt][r] = sc;
         mx = fmaxf(mx, sc);
       }
@@ -156,7 +174,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T*
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[kt][qt][r] *= inv;
-    if (hh == 0) lse[task * TOK + qi] = mx + __logf(sum);
+    if (hh == 0 && (TT == TOK || qi < TT)) lse[task * TT + qi] = mx + __logf(sum);
   }
   // O = P V : out tile [qt] rows = query, columns = d (lane)
 #pragma unroll
@@ -180,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const typename AT<BF>::T*
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int qi = qt * 32 + acc_row(r, hh);
-      O[(win * TOK + qi) * ldo + h * HDP + l31] = (T)(h * HDP + l31 == ones_col ? 1.f : o[r]);
+      if (TT == TOK || qi < TT) O[(win * TT + qi) * ldo + h * HDP + l31] = (T)(h * HDP + l31 == ones_col ? 1.f : o[r]);
     }
   }
 }
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __res
 // backward: one wave per (head, group of windows); dS summed over the group in registers for the
 // relative-position-bias gradient
 // ------------------------------------------------------------------------------------------
-template <bool BF>
+template <bool BF, int WSZ = WS>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T* __restrict__ qkv,
                                                        const typename AT<BF>::T* __restrict__ O, long ldo,
                                                        const typename AT<BF>::T* __restrict__ dO, long lddo,
@@ -349,13 +367,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
                                                        const float* __restrict__ amask, int mask_nw) {
   using T = typename AT<BF>::T;
   constexpr int LD = AT<BF>::LD;
-  constexpr int WAVES = NWAVES<BF>;
+  constexpr int WAVES = 2;   // (bf16: the generic backward serves window size 7 only; its tiles + the fp32 bias tile)
   constexpr int LDS_ = 72;  // dS tile row stride (bf16: 144 B; fp32 reads use 65)
+  constexpr int TT = WSZ * WSZ;   // real tokens of a window
   __shared__ __attribute__((aligned(16))) T sQ[WAVES][TOK * LD];
   __shared__ __attribute__((aligned(16))) T sK[WAVES][TOK * LD];
   __shared__ __attribute__((aligned(16))) T sV[WAVES][TOK * LD];
   __shared__ __attribute__((aligned(16))) T sdO[WAVES][TOK * LD];
-  __shared__ __attribute__((aligned(16))) T sdS[WAVES][TOK * (BF ? LDS_ : 65)];
+  // bf16: sized for the fp32 [64][65] bias-gradient tile that is binned through it after the last window
+  __shared__ __attribute__((aligned(16))) T sdS[WAVES][TOK * (BF ? 2 * 65 : 65)];
   __shared__ float sTab[WAVES][232];
   __shared__ float sRow[WAVES][2][TOK];  // lse, delta
   __shared__ int sReg[WAVES][TOK];
@@ -365,12 +385,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
   if (gtask >= ngroups * nh) return;
   const int h = (int)(gtask % nh);
   const long grp = gtask / nh;
-  const long M = nWin * TOK;
+  const long M = nWin * TT;
   const long part = M * nh * HDP;
   const int l31 = lane & 31, hh = lane >> 5;
   T* q = sQ[w]; T* k = sK[w]; T* v = sV[w]; T* go = sdO[w]; T* ds = sdS[w];
-  for (int i = lane; i < (2 * WS - 1) * (2 * WS - 1); i += 64) sTab[w][i] = table[i * nh + h];
-  const int nW = (H / WS) * (W / WS);
+  for (int i = lane; i < NBIN_W<WSZ>; i += 64) sTab[w][i] = table[i * nh + h];
+  const int nW = (H / WSZ) * (W / WSZ);
 
   // dS accumulator for the bias gradient: S-layout tiles [qt][kt], lane = key, regs = query
   f32x16 dB[2][2];
@@ -385,23 +405,26 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
   long w1 = w0 + wpg;
   if (w1 > nWin) w1 = nWin;
   for (long win = w0; win < w1; ++win) {
-    const long blk = (win * nh + h) * TOK * HDP;
+    const long blk = (win * nh + h) * TT * HDP;
     wave_sync();
-    stage_tile<BF>(q, qkv + blk, HDP, lane);
-    stage_tile<BF>(k, qkv + part + blk, HDP, lane);
-    stage_tile<BF>(v, qkv + 2 * part + blk, HDP, lane);
-    stage_tile<BF>(go, dO + win * TOK * lddo + h * HDP, lddo, lane);
-    {
+    stage_tile<BF, TT>(q, qkv + blk, HDP, lane);
+    stage_tile<BF, TT>(k, qkv + part + blk, HDP, lane);
+    stage_tile<BF, TT>(v, qkv + 2 * part + blk, HDP, lane);
+    stage_tile<BF, TT>(go, dO + win * TT * lddo + h * HDP, lddo, lane);
+    if (TT == TOK || lane < TT) {
       // delta[q] = sum_d dO[q][d] * O[q][d]  (lane = query)
-      const T* orow = O + (win * TOK + lane) * ldo + h * HDP;
-      const T* grow = dO + (win * TOK + lane) * lddo + h * HDP;
+      const T* orow = O + (win * TT + lane) * ldo + h * HDP;
+      const T* grow = dO + (win * TT + lane) * lddo + h * HDP;
       float d = 0.f;
 #pragma unroll
       for (int c = 0; c < HDP; ++c) d += (float)orow[c] * (float)grow[c];
       sRow[w][1][lane] = d;
-      sRow[w][0][lane] = lse[((long)win * nh + h) * TOK + lane];
-      sReg[w][lane] = shift > 0 ? token_region((int)(win % nW), lane, H, W, shift) : 0;
+      sRow[w][0][lane] = lse[((long)win * nh + h) * TT + lane];
+    } else {   // a pad query: defined (finite) row terms; its P is forced to 0 below
+      sRow[w][1][lane] = 0.f;
+      sRow[w][0][lane] = 0.f;
     }
+    sReg[w][lane] = shift > 0 ? token_region<WSZ>((int)(win % nW), lane, H, W, shift) : 0;
     wave_sync();
 
     // S = Q K^T and dP = dO V^T : tiles [qt][kt], lane = key, regs = query
@@ -456,8 +479,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
     // compile-time offset from a per-lane base: relidx(qi, ki) = 15 (4 qt + r/4) + r%4 + [15 (7 - ky)
     // + 7 - kx + 4 hh]; lse / delta / region of qi at [32 qt + 8 (r/4) + r%4] + 4 hh.  The reads
     // issue back to back instead of one dependent address computation each.
-    const int wi_img = (int)(win % nW), nWw = W / WS;
-    const bool mixed = shift > 0 && ((wi_img / nWw) == H / WS - 1 || (wi_img % nWw) == nWw - 1);
+    const int wi_img = (int)(win % nW), nWw = W / WSZ;
+    const bool mixed = shift > 0 && ((wi_img / nWw) == H / WSZ - 1 || (wi_img % nWw) == nWw - 1);
     const float* rl = &sRow[w][0][4 * hh];
     const float* rd = &sRow[w][1][4 * hh];
     const int* rg = &sReg[w][4 * hh];
@@ -465,16 +488,27 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
     for (int kt = 0; kt < 2; ++kt) {
       const int ki = kt * 32 + l31;
       const int rk = sReg[w][ki];
-      const float* tb = &sTab[w][15 * (WS - 1 - (ki >> 3)) + (WS - 1 - (ki & 7)) + 4 * hh];
+      const float* tb = nullptr;   // WSZ = 8: the compile-time-offset table base
+      if constexpr (TT == TOK) tb = &sTab[w][15 * (WS - 1 - (ki >> 3)) + (WS - 1 - (ki & 7)) + 4 * hh];
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int o = 32 * qt + 8 * (r >> 2) + (r & 3);
-          float sc = S[qt][kt][r] * scale + tb[15 * (4 * qt + (r >> 2)) + (r & 3)];
-          if (mixed && rg[o] != rk) sc += -100.f;
-          if (amask) sc += amask[((win % mask_nw) * TOK + qt * 32 + acc_row(r, hh)) * TOK + ki];
-          const float p = __expf(sc - rl[o]);
+          float p;
+          if constexpr (TT == TOK) {
+            float sc = S[qt][kt][r] * scale + tb[15 * (4 * qt + (r >> 2)) + (r & 3)];
+            if (mixed && rg[o] != rk) sc += -100.f;
+            if (amask) sc += amask[((win % mask_nw) * TOK + qt * 32 + acc_row(r, hh)) * TOK + ki];
+            p = __expf(sc - rl[o]);
+          } else {   // a pad query or key: P = 0 exactly, so dS = 0 * (0 - 0) = 0 (dO, v pad rows are zero)
+            const int qi = o + 4 * hh;
+            const bool real = qi < TT && ki < TT;
+            float sc = S[qt][kt][r] * scale + (real ? sTab[w][relidx<WSZ>(qi, ki)] : 0.f);
+            if (mixed && rg[o] != rk) sc += -100.f;
+            if (amask && real) sc += amask[((win % mask_nw) * TT + qi) * TT + ki];
+            p = real ? __expf(sc - rl[o]) : 0.f;
+          }
           S[qt][kt][r] = p;
           const float d = p * (dP[qt][kt][r] - rd[o]);
           dP[qt][kt][r] = d;
@@ -511,8 +545,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ki = kt * 32 + acc_row(r, hh);
-        dv_out[ki * HDP + l31] = (T)av[r];
-        dk_out[ki * HDP + l31] = (T)(ak[r] * scale);
+        if (TT == TOK || ki < TT) {
+          dv_out[ki * HDP + l31] = (T)av[r];
+          dk_out[ki * HDP + l31] = (T)(ak[r] * scale);
+        }
       }
     }
     // dQ = scale * dS K : dS through LDS ([q][key] row-major)
@@ -541,13 +577,14 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
                                                    0, 0, 0);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dq_out[(qt * 32 + acc_row(r, hh)) * HDP + l31] = (T)(aq[r] * scale);
+      for (int r = 0; r < 16; ++r)
+        if (TT == TOK || qt * 32 + acc_row(r, hh) < TT) dq_out[(qt * 32 + acc_row(r, hh)) * HDP + l31] = (T)(aq[r] * scale);
     }
   }
   // partial bias gradient of this (group, head): [q][key] through the wave's (free) dS tile, binned
   wave_sync();
-  float* dbt = (float*)sdS[w];   // fp32: [64][65]; bf16: [64][72] bf16 = [64][36] floats -- too small
-  static_assert(!BF, "the binned bias gradient needs the fp32 dS tile (the bf16 mode uses attn_bwd_bf16_kernel)");
+  float* dbt = (float*)sdS[w];   // [64][65] floats in either dtype
+  static_assert(sizeof(sdS[0]) >= TOK * 65 * sizeof(float) && sizeof(sQ[0]) >= 1024 * sizeof(float), "bias tile / bin scratch");
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -555,7 +592,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const typename AT<BF>::T*
 #pragma unroll
       for (int r = 0; r < 16; ++r) dbt[(qt * 32 + acc_row(r, hh)) * 65 + kt * 32 + l31] = dB[qt][kt][r];
   wave_sync();
-  bin_dbias<false>(dbt, 65, (float*)sQ[w], dB_part + (grp * nh + h) * NBIN, lane);
+  bin_dbias<false, WSZ>(dbt, 65, (float*)sQ[w], dB_part + (grp * nh + h) * NBIN_W<WSZ>, lane);
 }
 
 // perf-investigation phase stamps (KAIR_ATTN_STAMP=1, read with kair_debug_attn_stamps): per wave,
@@ -831,8 +868,11 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_bf16_kernel(const bf16* __re
 
 // dtable[idx][h] (+)= sum over groups of the binned per-group partials [group][h][idx] (coalesced,
 // one thread per (h, idx), the groups split over the 16 waves and summed in fixed order)
+// (NB: the bins of the window side, 225 or 169)
+template <int NB>
 __global__ __launch_bounds__(1024) void attn_dtable_sum_kernel(const float* __restrict__ part, long ngroups, int nh,
                                                                float* dtable, int acc) {
+  constexpr int NBIN = NB;
   const long n = (long)nh * NBIN;
   const long t = (long)blockIdx.x * 64 + (threadIdx.x & 63);
   const float s = split_sum16(part, ngroups, n, t, t < n);
@@ -845,7 +885,7 @@ __global__ __launch_bounds__(1024) void attn_dtable_sum_kernel(const float* __re
 
 // Grouped bias-table gradient (kair_attn_dtable_grouped): the sum above for every block of a group in
 // one launch; a workgroup finds its job by a scalar scan of the first-block offsets.
-struct DtabJob { const float* part; float* dtable; long ngroups; int nh, acc, blk0; };
+struct DtabJob { const float* part; float* dtable; long ngroups; int nh, acc, blk0, nbin; };
 constexpr int DTAB_MAX = 32;
 struct DtabGroup { DtabJob j[DTAB_MAX]; int njobs; };
 
@@ -858,6 +898,7 @@ KAIR_DEV int dtab_job(const DtabGroup& g, int b) {
 
 __global__ __launch_bounds__(1024) void attn_dtable_grouped(const DtabGroup g) {
   const DtabJob& jb = g.j[dtab_job(g, blockIdx.x)];
+  const int NBIN = jb.nbin;   // per job: blocks of both window sides may share a launch
   const long n = (long)jb.nh * NBIN;
   const long t = (long)(blockIdx.x - jb.blk0) * 64 + (threadIdx.x & 63);
   const float s = split_sum16(jb.part, jb.ngroups, n, t, t < n);
@@ -908,23 +949,33 @@ static int fwd_tpw_bf16(long tasks, int occ) {
 
 }  // namespace
 
-extern "C" int kair_window_attn_fwd_ex(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
-                                       long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
-                                       const float* mask, int mask_nw, int head_pad, void* stream) {
+extern "C" int kair_window_attn_fwd_w(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
+                                      long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
+                                      const float* mask, int mask_nw, int head_pad, int ws, void* stream) {
+  KAIR_CHECK_ARG(attn_ws_ok(ws), "window_attn_fwd: window size %d (7 or 8)", ws);
   KAIR_CHECK_ARG(!mask || (mask_nw > 0 && shift == 0), "window_attn_fwd: an explicit mask needs mask_nw > 0 and shift 0");
   KAIR_CHECK_ARG(qkv && table && O && lse, "window_attn_fwd: null pointer");
   KAIR_CHECK_ARG(head_pad == HDP || (head_pad == 16 && dtype == KAIR_BF16), "window_attn_fwd: head pad %d (32, or 16 in bf16)",
                  head_pad);
   const int hp = head_pad;
   KAIR_CHECK_ARG(hd > 0 && hd <= hp && nh > 0 && nWin > 0, "window_attn_fwd: head_dim %d must be <= %d", hd, hp);
-  KAIR_CHECK_ARG(H % WS == 0 && W % WS == 0 && (shift == 0 || (shift > 0 && shift < WS)),
-                 "window_attn_fwd: grid %dx%d / shift %d", H, W, shift);
+  KAIR_CHECK_ARG(H > 0 && W > 0 && H % ws == 0 && W % ws == 0 && (shift == 0 || (shift > 0 && shift < ws)),
+                 "window_attn_fwd: grid %dx%d / shift %d at window size %d", H, W, shift, ws);
   KAIR_CHECK_ARG(ldo >= nh * hp && ldo % 8 == 0, "window_attn_fwd: ldo");
+  KAIR_CHECK_ARG(ws == WS || hp == HDP, "window_attn_fwd: window size 7 takes the head pad 32 layout");
   KAIR_CHECK_ARG(ones_col < 0 || (ones_col < nh * hp && ones_col % hp >= hd), "window_attn_fwd: ones column must be a pad column");
   const long tasks = nWin * nh;
   const int nw = dtype == KAIR_BF16 ? NWAVES<true> : NWAVES<false>;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == KAIR_BF16) {
+  if (ws == 7) {   // the generic pair in either dtype (the tuned bf16 kernels are 8 x 8 only)
+    const long nb = (tasks + nw - 1) / nw;
+    if (dtype == KAIR_BF16)
+      KAIR_LAUNCH((attn_fwd_kernel<true, 7>), dim3((unsigned)nb), dim3(64 * nw), 0, s, (const bf16*)qkv, table, (bf16*)O, ldo,
+                  lse, nWin, nh, scale, H, W, shift, ones_col, mask, mask_nw);
+    else
+      KAIR_LAUNCH((attn_fwd_kernel<false, 7>), dim3((unsigned)nb), dim3(64 * nw), 0, s, (const float*)qkv, table, (float*)O,
+                  ldo, lse, nWin, nh, scale, H, W, shift, ones_col, mask, mask_nw);
+  } else if (dtype == KAIR_BF16) {
     const int tpw = fwd_tpw_bf16(tasks, hp == 16 ? 3 : 2);
     const long nb = (tasks + (long)nw * tpw - 1) / ((long)nw * tpw);
     if (hp == 16)
@@ -940,6 +991,13 @@ extern "C" int kair_window_attn_fwd_ex(const void* qkv, int dtype, const float* 
   }
   KAIR_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int kair_window_attn_fwd_ex(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
+                                       long nWin, int nh, int hd, float scale, int H, int W, int shift, int ones_col,
+                                       const float* mask, int mask_nw, int head_pad, void* stream) {
+  return kair_window_attn_fwd_w(qkv, dtype, table, O, ldo, lse, nWin, nh, hd, scale, H, W, shift, ones_col, mask, mask_nw,
+                                head_pad, WS, stream);
 }
 
 extern "C" int kair_window_attn_fwd(const void* qkv, int dtype, const float* table, void* O, long ldo, float* lse,
@@ -966,39 +1024,56 @@ extern "C" int kair_debug_attn_stamps(unsigned long long* host, int n) {
   return 0;
 }
 
-extern "C" long kair_window_attn_bwd_ws(long nWin, int nh) {
+// (0 for an unsupported window side: no workspace to size)
+extern "C" long kair_window_attn_bwd_ws_w(long nWin, int nh, int ws) {
+  if (!attn_ws_ok(ws)) return 0;
   const long g32 = bwd_groups(nWin, WPG), g16 = bwd_groups(nWin, bwd_wpg_bf16(nWin, nh));
   const long gx3 = bwd_groups(nWin, (int)kair_attn_x3_wpg(nWin, nh));
   long g = g32 > g16 ? g32 : g16;
   if (gx3 > g) g = gx3;
-  return g * nh * NBIN;
+  return g * nh * (ws == 7 ? NBIN_W<7> : NBIN);
 }
 
-int kair_attn_dtable_sum(const float* ws, long ngroups, int nh, float* dtable, int accumulate, hipStream_t s) {
-  KAIR_LAUNCH(attn_dtable_sum_kernel, dim3((nh * NBIN + 63) / 64), dim3(1024), 0, s, ws, ngroups, nh, dtable,
+extern "C" long kair_window_attn_bwd_ws(long nWin, int nh) { return kair_window_attn_bwd_ws_w(nWin, nh, WS); }
+
+int kair_attn_dtable_sum(const float* ws, long ngroups, int nh, float* dtable, int accumulate, hipStream_t s, int win_ws) {
+  if (win_ws == 7)
+    KAIR_LAUNCH(attn_dtable_sum_kernel<NBIN_W<7>>, dim3((nh * NBIN_W<7> + 63) / 64), dim3(1024), 0, s, ws, ngroups, nh, dtable,
+                accumulate);
+  else
+    KAIR_LAUNCH(attn_dtable_sum_kernel<NBIN>, dim3((nh * NBIN + 63) / 64), dim3(1024), 0, s, ws, ngroups, nh, dtable,
                      accumulate);
   KAIR_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int kair_window_attn_bwd_ex(const void* qkv, const void* O, long ldo, const void* dO, long lddo, int dtype,
-                                       const float* table, const float* lse, void* dqkv, int dqkv_rows, float* dtable,
-                                       int dtable_accumulate, float* ws, long nWin, int nh, int hd, float scale, int H, int W,
-                                       int shift, const float* mask, int mask_nw, int head_pad, void* stream) {
+extern "C" int kair_window_attn_bwd_w(const void* qkv, const void* O, long ldo, const void* dO, long lddo, int dtype,
+                                      const float* table, const float* lse, void* dqkv, int dqkv_rows, float* dtable,
+                                      int dtable_accumulate, float* ws, long nWin, int nh, int hd, float scale, int H, int W,
+                                      int shift, const float* mask, int mask_nw, int head_pad, int win_ws, void* stream) {
+  KAIR_CHECK_ARG(attn_ws_ok(win_ws), "window_attn_bwd: window size %d (7 or 8)", win_ws);
   KAIR_CHECK_ARG(!dqkv_rows || dtype == KAIR_BF16, "window_attn_bwd: token-row dqkv is a bf16 layout");
   KAIR_CHECK_ARG(head_pad == HDP || (head_pad == 16 && dtype == KAIR_BF16), "window_attn_bwd: head pad %d (32, or 16 in bf16)",
                  head_pad);
   KAIR_CHECK_ARG(!mask || (mask_nw > 0 && shift == 0), "window_attn_bwd: an explicit mask needs mask_nw > 0 and shift 0");
   KAIR_CHECK_ARG(qkv && O && dO && table && lse && dqkv && ws, "window_attn_bwd: null pointer");
   KAIR_CHECK_ARG(hd > 0 && hd <= head_pad && nh > 0 && nWin > 0, "window_attn_bwd: head_dim");
-  KAIR_CHECK_ARG(H % WS == 0 && W % WS == 0 && (shift == 0 || (shift > 0 && shift < WS)), "window_attn_bwd: geometry");
+  KAIR_CHECK_ARG(H > 0 && W > 0 && H % win_ws == 0 && W % win_ws == 0 && (shift == 0 || (shift > 0 && shift < win_ws)),
+                 "window_attn_bwd: grid %dx%d / shift %d at window size %d", H, W, shift, win_ws);
   KAIR_CHECK_ARG(ldo % 8 == 0 && lddo % 8 == 0, "window_attn_bwd: strides");
+  KAIR_CHECK_ARG(win_ws == WS || (!dqkv_rows && head_pad == HDP), "window_attn_bwd: window size 7 takes head-blocked dqkv, head pad 32");
   const int wpg = dtype == KAIR_BF16 ? bwd_wpg_bf16(nWin, nh) : WPG;
   const long ngroups = bwd_groups(nWin, wpg);
-  const int nw = dtype == KAIR_BF16 ? g_bwd_nw : NWAVES<false>;
+  const int nw = dtype == KAIR_BF16 && win_ws == WS ? g_bwd_nw : NWAVES<false>;   // (the generic kernel: 2 waves)
   const long nb = (ngroups * nh + nw - 1) / nw;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == KAIR_BF16 && head_pad == 16)
+  if (win_ws == 7 && dtype == KAIR_BF16)   // the generic pair (the tuned bf16 kernels are 8 x 8 only)
+    KAIR_LAUNCH((attn_bwd_kernel<true, 7>), dim3((unsigned)nb), dim3(64 * nw), 0, s, (const bf16*)qkv, (const bf16*)O,
+                ldo, (const bf16*)dO, lddo, table, lse, (bf16*)dqkv, ws, nWin, nh, wpg, scale, H, W, shift, mask, mask_nw);
+  else if (win_ws == 7)
+    KAIR_LAUNCH((attn_bwd_kernel<false, 7>), dim3((unsigned)nb), dim3(64 * nw), 0, s, (const float*)qkv, (const float*)O,
+                ldo, (const float*)dO, lddo, table, lse, (float*)dqkv, ws, nWin, nh, wpg, scale, H, W, shift, mask, mask_nw);
+  else if (dtype == KAIR_BF16 && head_pad == 16)
     KAIR_LAUNCH((attn_bwd_bf16_kernel<2, 16>), dim3((unsigned)nb), dim3(64 * nw), 0, s, (const bf16*)qkv, (const bf16*)O,
                        ldo, (const bf16*)dO, lddo, table, lse, (bf16*)dqkv, ws, nWin, nh, wpg, scale, H, W, shift, mask,
                        mask_nw, g_stamp, dqkv_rows);
@@ -1015,10 +1090,15 @@ extern "C" int kair_window_attn_bwd_ex(const void* qkv, const void* O, long ldo,
                        ldo, (const float*)dO, lddo, table, lse, (float*)dqkv, ws, nWin, nh, wpg, scale, H, W, shift, mask, mask_nw);
   KAIR_CHECK_LAUNCH();
   if (!dtable) return 0;   // deferred: the per-group partials stay in ws for kair_attn_dtable_grouped
-  KAIR_LAUNCH(attn_dtable_sum_kernel, dim3((nh * NBIN + 63) / 64), dim3(1024), 0, s, ws, ngroups, nh, dtable,
-                     dtable_accumulate);
-  KAIR_CHECK_LAUNCH();
-  return 0;
+  return kair_attn_dtable_sum(ws, ngroups, nh, dtable, dtable_accumulate, s, win_ws);
+}
+
+extern "C" int kair_window_attn_bwd_ex(const void* qkv, const void* O, long ldo, const void* dO, long lddo, int dtype,
+                                       const float* table, const float* lse, void* dqkv, int dqkv_rows, float* dtable,
+                                       int dtable_accumulate, float* ws, long nWin, int nh, int hd, float scale, int H, int W,
+                                       int shift, const float* mask, int mask_nw, int head_pad, void* stream) {
+  return kair_window_attn_bwd_w(qkv, O, ldo, dO, lddo, dtype, table, lse, dqkv, dqkv_rows, dtable, dtable_accumulate, ws, nWin,
+                                nh, hd, scale, H, W, shift, mask, mask_nw, head_pad, WS, stream);
 }
 
 extern "C" int kair_window_attn_bwd(const void* qkv, const void* O, long ldo, const void* dO, long lddo, int dtype,
@@ -1043,8 +1123,10 @@ extern "C" int kair_attn_dtable_grouped(const kair_attn_dtable_job* jobs, int nj
   for (int i = 0; i < njobs; ++i) {
     const kair_attn_dtable_job& J = jobs[i];
     KAIR_CHECK_ARG(J.ws && J.dtable && J.nh > 0 && J.nWin > 0, "attn_dtable_grouped: job %d", i);
-    g.j[i] = DtabJob{J.ws, J.dtable, kair_window_attn_bwd_groups(J.nWin, J.nh, J.dtype), J.nh, J.accumulate ? 1 : 0, b0};
-    b0 += (J.nh * NBIN + 63) / 64;
+    KAIR_CHECK_ARG(J.win_ws == 0 || attn_ws_ok(J.win_ws), "attn_dtable_grouped: job %d window size %d (0 = 8, 7 or 8)", i, J.win_ws);
+    const int nbin = J.win_ws == 7 ? NBIN_W<7> : NBIN;
+    g.j[i] = DtabJob{J.ws, J.dtable, kair_window_attn_bwd_groups(J.nWin, J.nh, J.dtype), J.nh, J.accumulate ? 1 : 0, b0, nbin};
+    b0 += (J.nh * nbin + 63) / 64;
   }
   g.njobs = njobs;
   hipStream_t s = (hipStream_t)stream;

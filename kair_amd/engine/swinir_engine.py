@@ -25,7 +25,7 @@ import torch
 from .. import _hip as H
 from .plans import Lease, PlanPool, autograd_mode, plan_mode
 
-WS_TOK = 64
+WINDOW_SIZES = (7, 8)    # the window sides the attention kernels are built for
 
 
 def _rup(x, m):
@@ -316,21 +316,29 @@ class SwinIREngine:
         if hd >= 32 or self.C % self.nh:
             raise NotImplementedError("kair_amd SwinIR: head_dim must be < 32")
         self.ws = net.window_size
-        if self.ws != 8:
-            raise NotImplementedError("kair_amd SwinIR: window_size 8 only (fused attention tile)")
+        if self.ws not in WINDOW_SIZES:
+            raise NotImplementedError(f"kair_amd SwinIR: window_size {self.ws}: the attention kernels are built for "
+                                      f"window sizes 7 and 8")
+        self.T = self.ws * self.ws   # tokens per window: every window-ordered layout is dense in T
+        # the kernels specialised to the 8 x 8 geometry (the fused block halves, the row GEMMs, the head pad 16
+        # attention kernels) run at window size 8 only; other sizes take the unfused launch sequence (bf16: the
+        # generic attention pair, head pad 32, head-blocked dq/dk/dv)
+        ws8 = self.ws == 8
         self.Cp = _rup(self.C + 1, 32)
-        self.fused_attn = bool(fused_blocks) and compute_dtype == "bf16" and self.nh == 6 and self.Cp == 32 * self.nh
+        self.fused_attn = (bool(fused_blocks) and compute_dtype == "bf16" and self.nh == 6 and self.Cp == 32 * self.nh
+                           and ws8)
         Hd = net.layers[0].residual_group.blocks[0].mlp.fc1.out_features
         self.Hdp = _rup(Hd + 1, 32)
         # fused_mlp=False: the LN2 / fc1 / fc2 launches instead of the fused MLP half (A/B timing).  Every
         # engine variant is a constructor argument: no environment variable changes what the engine runs
         if fused_mlp is None:
             fused_mlp = fused_blocks
-        self.fused_mlp = bool(fused_mlp) and compute_dtype == "bf16" and self.Cp == 192 and self.Hdp == 384
+        self.fused_mlp = bool(fused_mlp) and compute_dtype == "bf16" and self.Cp == 192 and self.Hdp == 384 and ws8
         # head pad of the q/k/v / O / dO layouts: 16 for head dims below 16 on the unfused bf16 path (SwinIR-lightweight,
         # 60 / 6 = 10: half the attention bytes of a 32 pad, kair_window_attn_fwd_ex), else 32; head_pad=32 forces the
         # wide layout (A/B timing, parity of both layouts)
-        hp16 = compute_dtype == "bf16" and hd < 16 and not self.fused_attn and not (self.Cp == 192 and self.Hdp == 384)
+        hp16 = (compute_dtype == "bf16" and hd < 16 and not self.fused_attn and not (self.Cp == 192 and self.Hdp == 384)
+                and ws8)
         self.hp = 16 if hp16 and head_pad in (None, 16) else 32
         if head_pad not in (None, 16, 32) or (head_pad == 16 and self.hp != 16):
             raise ValueError(f"head_pad {head_pad}: 32, or 16 for bf16 head dims below 16 on the unfused path")
@@ -338,7 +346,7 @@ class SwinIREngine:
         # for the fc2 / fc1 input-gradient GEMMs + LN2 backward it replaces (its memory
         # waves' LayerNorm rows and the tile loads run latency-exposed); fused_mlp_bwd=True enables it
         self.fused_mlp_bwd = (bool(fused_blocks) and compute_dtype == "bf16" and self.Cp == 192 and self.Hdp == 384
-                              and bool(fused_mlp_bwd))
+                              and bool(fused_mlp_bwd) and ws8)
         # split linears measured: the PSNR effect of bf16 linear-weight rounding is ~1e-4 dB against
         # ~5e-4 dB of activation-rounding noise per image (tools/parity_seeds.py, DESIGN.md "parity at
         # bf16"), at +45 us per block for the attention kernel -- off unless asked for
@@ -347,7 +355,8 @@ class SwinIREngine:
         # fc2 (GELU' gate), fc1 + LayerNorm-2 backward, proj, q/k/v + LayerNorm-1 backward -- bf16, Cp = 192
         # geometry (classical / real-world x4); other widths run the same products on kair_gemm_nt +
         # kair_layernorm_bwd.  No library GEMM is on the training path.
-        self.rowgemm = (compute_dtype == "bf16" and self.Cp == 192 and self.Hdp == 384 and self.nh * self.hp == self.Cp)
+        self.rowgemm = (compute_dtype == "bf16" and self.Cp == 192 and self.Hdp == 384 and self.nh * self.hp == self.Cp
+                        and ws8)
         self.upsampler, self.scale = net.upsampler, net.upscale
         self.in_ch = net.conv_first.in_channels
         self.img_range = float(net.img_range)
@@ -520,7 +529,9 @@ class SwinIREngine:
         dev, T, f32 = self.device, self.tdt, torch.float32
         M = B * Hh * Ww
         Cp, Hdp, nh, hp = self.Cp, self.Hdp, self.nh, self.hp
-        nWin = M // WS_TOK
+        if Hh % self.ws or Ww % self.ws:
+            raise ValueError(f"kair_amd SwinIR: the {Hh}x{Ww} token grid is no multiple of window_size {self.ws}")
+        nWin = M // self.T
         e = lambda *s, dt=f32: torch.empty(*s, device=dev, dtype=dt)
         hf = torch.float16
         P = {"B": B, "H": Hh, "W": Ww, "M": M, "nWin": nWin}
@@ -542,7 +553,7 @@ class SwinIREngine:
             blocks.append({
                 "mid": e(M, Cp), "out": e(M, Cp), "ln1": pr(M, Cp), "m1": e(M), "r1": e(M),
                 "qkv": e(2, 3 * M * nh * hp, dt=hf) if self.x3 else e(3 * M * nh * hp, dt=T),
-                "O": pr(M, nh * hp), "lse": e(nWin * nh * WS_TOK),
+                "O": pr(M, nh * hp), "lse": e(nWin * nh * self.T),
                 "ln2": pr(M, Cp), "m2": e(M), "r2": e(M), "u": e(M, Hdp, dt=T), "h": pr(M, Hdp)})
         P["blocks"] = blocks
         P["rstb_out"] = [e(M, Cp) for _ in range(min(2, len(self.rstb)) if infer else len(self.rstb))]
@@ -603,7 +614,7 @@ class SwinIREngine:
                      "dqkv": ep(M, 3 * nh * hp) if self.x3 else e(3 * M * nh * hp, dt=T),
                      # LN1 / LN2 parameter partials and the attention bias-table partials of the block, reduced
                      # by one grouped launch each at the end of the RSTB
-                     "ln1p": e(lnp), "ln2p": e(lnp), "attn_ws": e(H.window_attn_bwd_ws(nWin, nh))}
+                     "ln1p": e(lnp), "ln2p": e(lnp), "attn_ws": e(H.window_attn_bwd_ws(nWin, nh, self.ws))}
                     for _ in range(depth)] for _ in range(2)]
         P["G3"] = z32(M, Cp)   # third residual-gradient buffer (rotation, see backward())
         if self.rowgemm:   # LayerNorm-parameter partial rows the fused row GEMMs leave (<= the ln*p buffers' 2048)
@@ -611,7 +622,7 @@ class SwinIREngine:
             assert max(P["rg_nb"].values()) <= 2048, P["rg_nb"]
         P["dO"] = e(2, M, nh * hp, dt=hf) if self.x3 else e(M, nh * hp, dt=T)
         P["ln_ws"] = e(2 * 2048 * Cp)   # kair_layernorm_bwd: 2 * 2048 * C floats
-        P["attn_ws"] = e(H.window_attn_bwd_ws(nWin, nh))
+        P["attn_ws"] = e(H.window_attn_bwd_ws(nWin, nh, self.ws))
         P["loss"] = e(1)
         P["loss_ws"] = e(1024)
         P["colsum_ws"] = e(1024 * 256)
@@ -709,7 +720,7 @@ class SwinIREngine:
     # forward
     # ------------------------------------------------------------------------------------
     def forward(self, x, drop_scales=None):
-        """x: [B, in_ch, H, W] fp32 on the device (H, W multiples of 8).  Returns P['E'] (NCHW fp32).
+        """x: [B, in_ch, H, W] fp32 on the device (H, W multiples of the window size).  Returns P['E'] (NCHW fp32).
         drop_scales: optional [nblocks, 2, B] fp32 DropPath scales (0 or 1/keep)."""
         B, _, Hh, Ww = x.shape
         P = self.plan(B, Hh, Ww)
@@ -940,7 +951,7 @@ class SwinIREngine:
         cd = self.cd
         M, Cp, nh, hp, Hh, Ww = P["M"], self.Cp, self.nh, self.hp, P["H"], P["W"]
         HW = Hh * Ww
-        win = (Hh, Ww, 8, blk.shift)
+        win = (Hh, Ww, self.ws, blk.shift)
         drop = P["drop"]
         s_attn = drop[bi, 0] if drop is not None else None
         s_mlp = drop[bi, 1] if drop is not None else None
@@ -961,16 +972,17 @@ class SwinIREngine:
             l = blk.qkv
             if self.x3:   # q/k/v as hi/lo planes into the split attention kernels, O out as a pair too
                 self._nt(self._op(S["ln1"]), H.rows(l.Wp), H.epilogue(S["qkv"][0], mode=H.OUT_QKVBLK, ldo=0, bias=l.bp,
-                                                                       qkv=(nh, 32, WS_TOK), out_lo=S["qkv"][1]),
+                                                                       qkv=(nh, 32, self.T), out_lo=S["qkv"][1]),
                          M, l.Np, Cp, cd)
                 H.window_attn_fwd_x3(S["qkv"], blk.table, S["O"], nh * 32, S["lse"], P["nWin"], nh, self.C // nh, blk.scale,
-                                     Hh, Ww, blk.shift, ones_col=self.C // nh, e_in=self.X3_AEXP, e_out=self.X3_AEXP)
+                                     Hh, Ww, blk.shift, ones_col=self.C // nh, e_in=self.X3_AEXP, e_out=self.X3_AEXP,
+                                     ws=self.ws)
                 A_o = self._op(S["O"])
             else:
                 self._nt(H.rows(S["ln1"]), H.rows(l.Wp), H.epilogue(S["qkv"], mode=H.OUT_QKVBLK, ldo=0, bias=l.bp,
-                                                                     qkv=(nh, hp, WS_TOK)), M, l.Np, Cp, cd)
+                                                                     qkv=(nh, hp, self.T)), M, l.Np, Cp, cd)
                 H.window_attn_fwd(S["qkv"], blk.table, S["O"], nh * hp, S["lse"], P["nWin"], nh, self.C // nh, blk.scale,
-                                  Hh, Ww, blk.shift, ones_col=self.C // nh, head_pad=hp)
+                                  Hh, Ww, blk.shift, ones_col=self.C // nh, head_pad=hp, ws=self.ws)
                 A_o = H.rows(S["O"])
             l = blk.proj
             self._nt(A_o, H.rows(l.Wp), H.epilogue(S["mid"], win=win, bias=l.bp, resid=x, rowscale=s_attn,
@@ -1308,7 +1320,7 @@ class SwinIREngine:
         cd, g = self.cd, (lambda p: grads[p])
         M, Cp, nh, Hh, Ww = P["M"], self.Cp, self.nh, P["H"], P["W"]
         HW = Hh * Ww
-        win = (Hh, Ww, 8, blk.shift)
+        win = (Hh, Ww, self.ws, blk.shift)
         drop = P["drop"]
         s_attn = drop[bi, 0] if drop is not None else None
         hd = self.C // nh
@@ -1359,9 +1371,10 @@ class SwinIREngine:
             self._nt(H.rows(Da), H.rows(proj.Wt), H.epilogue(P["dO"]), M, nh * hp, Cp, cd)
         rows = self.rowgemm   # dq/dk/dv as token rows [M][3 nh 32]: the row GEMM's A operand
         H.window_attn_bwd(S["qkv"], S["O"], nh * hp, P["dO"], nh * hp, blk.table, S["lse"], dqkv, None, False,
-                          W["attn_ws"], P["nWin"], nh, hd, blk.scale, Hh, Ww, blk.shift, dqkv_rows=rows, head_pad=hp)
-        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, self.cd, g(blk.table), False))
-        A_qkv = H.rows(dqkv.view(M, qkv.Np)) if rows else H.qkvblk(dqkv, nh, hdp=hp)
+                          W["attn_ws"], P["nWin"], nh, hd, blk.scale, Hh, Ww, blk.shift, dqkv_rows=rows, head_pad=hp,
+                          win_ws=self.ws)
+        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, self.cd, g(blk.table), False, self.ws))
+        A_qkv = H.rows(dqkv.view(M, qkv.Np)) if rows else H.qkvblk(dqkv, nh, hdp=hp, ws=self.ws)
         self._wg(P, A_qkv, H.rows(S["ln1"], ones_col=self.C, ones_in_data=True), qkv.Np, Cp, qkv, grads, self.C)
         n = blk.n1
         cp = None
@@ -1374,7 +1387,7 @@ class SwinIREngine:
                             W["ln1p"], win=win, copy=cp)
             self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False, P["rg_nb"][qkv.Np]))
         else:
-            self._nt(H.qkvblk(dqkv, nh, hdp=hp), H.rows(qkv.Wt), H.epilogue(P["dxn"]), M, Cp, qkv.Np, cd)
+            self._nt(H.qkvblk(dqkv, nh, hdp=hp, ws=self.ws), H.rows(qkv.Wt), H.epilogue(P["dxn"]), M, Cp, qkv.Np, cd)
             H.layernorm_bwd(x_in, Cp, P["dxn"], Cp, n.weight, S["m1"], S["r1"], D, Cp, True, None, None, False,
                             W["ln1p"], M, self.C, win, copy=cp)
             self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False))
@@ -1386,7 +1399,7 @@ class SwinIREngine:
         cd, g = self.cd, (lambda p: grads[p])
         M, Cp, nh, Hh, Ww = P["M"], self.Cp, self.nh, P["H"], P["W"]
         HW = Hh * Ww
-        win = (Hh, Ww, 8, blk.shift)
+        win = (Hh, Ww, self.ws, blk.shift)
         drop = P["drop"]
         hd = self.C // nh
         W = P["gw"][par][j]
@@ -1396,8 +1409,8 @@ class SwinIREngine:
         self._nt(self._op(Da), H.rows(proj.Wt), H.epilogue(P["dO"][0], out_lo=P["dO"][1]), M, nh * 32, Cp, cd)
         H.window_attn_bwd_x3(S["qkv"], S["O"], nh * 32, P["dO"], nh * 32, blk.table, S["lse"], dqkv, None, False,
                              W["attn_ws"], P["nWin"], nh, hd, blk.scale, Hh, Ww, blk.shift, e_act=self.X3_AEXP,
-                             e_grad=P["e_g"])
-        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, H.X3, g(blk.table), False))
+                             e_grad=P["e_g"], win_ws=self.ws)
+        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, H.X3, g(blk.table), False, self.ws))
         self._wg(P, self._op(dqkv), self._op(S["ln1"], ones_col=self.C, ones_in_data=True), qkv.Np, Cp, qkv, grads, self.C)
         n = blk.n1
         cp = None

@@ -138,7 +138,7 @@ torch.library.register_autograd("kair::linear", _linear_backward, setup_context=
 # window attention core: softmax(q*scale k^T + rel-pos bias (+ mask)) v per (window, head)
 # ------------------------------------------------------------------------------------------
 def _qkv_blocked(qkv, nh, T):
-    """[B_, 64, 3C] -> head-blocked, head-padded [3][B_][nh][64][32] (the kernels' layout)."""
+    """[B_, N, 3C] -> head-blocked, head-padded [3][B_][nh][N][32] (the kernels' layout; N = 64 or 49)."""
     B_, N, C3 = qkv.shape
     hd = C3 // (3 * nh)
     v = qkv.reshape(B_, N, 3, nh, hd).permute(2, 0, 3, 1, 4)
@@ -149,10 +149,15 @@ def _qkv_blocked(qkv, nh, T):
 
 def _check_attn(qkv, nh, mask):
     B_, N, C3 = qkv.shape
-    if N != 64 or C3 % (3 * nh) or C3 // (3 * nh) > 32:
-        raise RuntimeError(f"kair::window_attn: 8x8 windows and head_dim <= 32 only (got N={N}, 3C={C3}, nh={nh})")
-    if mask is not None and (mask.dim() != 3 or mask.shape[1:] != (64, 64) or B_ % mask.shape[0]):
-        raise RuntimeError("kair::window_attn: mask must be [nW, 64, 64] with nW dividing the window count")
+    if N not in (49, 64) or C3 % (3 * nh) or C3 // (3 * nh) > 32:
+        raise RuntimeError(f"kair::window_attn: 8x8 or 7x7 windows and head_dim <= 32 only (got N={N}, 3C={C3}, nh={nh})")
+    if mask is not None and (mask.dim() != 3 or mask.shape[1:] != (N, N) or B_ % mask.shape[0]):
+        raise RuntimeError(f"kair::window_attn: mask must be [nW, {N}, {N}] with nW dividing the window count")
+
+
+def _ws_of(N):
+    """The window side of N tokens per window (64 -> 8, 49 -> 7)."""
+    return 7 if N == 49 else 8
 
 
 @torch.library.custom_op("kair::window_attn", mutates_args=(), device_types="cuda")
@@ -165,8 +170,9 @@ def window_attn(qkv: Tensor, table: Tensor, mask: Optional[Tensor], nh: int, sca
     o_pad = torch.empty(B_ * N, nh * 32, device=qkv.device, dtype=T)
     lse = torch.empty(B_, nh, N, device=qkv.device)
     m = mask.float().contiguous() if mask is not None else None
-    H.window_attn_fwd(blk, table.detach().float().contiguous(), o_pad, nh * 32, lse, B_, nh, hd, scale, 8, 8, 0,
-                      mask=m)
+    ws = _ws_of(N)
+    H.window_attn_fwd(blk, table.detach().float().contiguous(), o_pad, nh * 32, lse, B_, nh, hd, scale, ws, ws, 0,
+                      mask=m, ws=ws)
     o = o_pad.view(B_, N, nh, 32)[..., :hd].reshape(B_, N, C).float()
     return o, lse, o_pad
 
@@ -188,10 +194,11 @@ def window_attn_bwd(go: Tensor, qkv: Tensor, table: Tensor, mask: Optional[Tenso
     dO[..., :hd] = go.reshape(B_, N, nh, hd)
     dblk = torch.empty_like(blk)
     dtable = torch.empty_like(table, dtype=torch.float32)
-    ws = torch.empty(H.window_attn_bwd_ws(B_, nh), device=qkv.device)
+    wsz = _ws_of(N)
+    ws = torch.empty(H.window_attn_bwd_ws(B_, nh, wsz), device=qkv.device)
     m = mask.float().contiguous() if mask is not None else None
     H.window_attn_bwd(blk, o_pad, nh * 32, dO.view(B_ * N, nh * 32), nh * 32, table.detach().float().contiguous(), lse,
-                      dblk, dtable, False, ws, B_, nh, hd, scale, 8, 8, 0, mask=m)
+                      dblk, dtable, False, ws, B_, nh, hd, scale, wsz, wsz, 0, mask=m, win_ws=wsz)
     gqkv = dblk[..., :hd].permute(1, 3, 0, 2, 4).reshape(B_, N, C3).float()
     return gqkv, dtable
 

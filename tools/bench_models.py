@@ -1,13 +1,16 @@
 """Training throughput of the other BASELINE.json configs on one MI355X (the headline SwinIR
 classical x4 line is bench.py's).  One JSON line per config:
 
-    python tools/bench_models.py [dncnn|swinir_light|rrdbnet|usrnet ...] [--steps K] [--warmup W]
+    python tools/bench_models.py [dncnn|swinir_light|rrdbnet|usrnet|swinir_jpeg ...] [--steps K] [--warmup W]
 
 C1 DnCNN sigma 25, 40x40, batch 64 (BN, fused trainer)        network_dncnn.py, options/train_dncnn.json
 C2 SwinIR-lightweight x2, 64-px LQ, batch 64 (fused trainer)   options/swinir/train_swinir_sr_lightweight.json
 C5 RRDBNet x4, 32-px LQ, batch 16 (fused trainer)              options/train_rrdb_psnr.json
 C3 USRNet x4, 128-px LQ (512^2 HR), batch 48, n_iter 6         options/train_usrnet.json (ModelPlain4 step:
                                                                 fused trainer with (k, sf, sigma) inputs, no EMA)
+   SwinIR JPEG artifact reduction, gray, 126-px patches, window 7, batch 8   options/swinir/train_swinir_car_jpeg.json
+                                                                (not in BASELINE.json: FLOPs from
+                                                                swinir_engine.swinir_flops, no throughput target)
 Synthetic seeded inputs resident in HBM; bf16 MFMA operands, fp32 accumulation.
 FLOP/patch from BASELINE.md (FlopCounterMode, GEMM + conv only; USRNet FFTs not counted).
 """
@@ -53,6 +56,14 @@ def run(name, steps, warmup, dev, dtype="bf16", head_pad=None, grouped_wgrad=Non
                             embed_dim=60, num_heads=[6] * 4, mlp_ratio=2, upsampler="pixelshuffledirect",
                             resi_connection="1conv", compute_dtype=dtype)
         B, shp, sc = 64, (3, 64, 64), 2
+    elif name == "swinir_jpeg":
+        from kair_amd.engine.swinir_engine import swinir_flops
+        from kair_amd.models.network_swinir import SwinIR
+        mk = lambda: SwinIR(upscale=1, in_chans=1, img_size=126, window_size=7, img_range=255.0, depths=[6] * 6,   # noqa: E731
+                            embed_dim=180, num_heads=[6] * 6, mlp_ratio=2, upsampler=None, resi_connection="1conv",
+                            compute_dtype=dtype)
+        B, shp, sc = 8, (1, 126, 126), 1
+        TRAIN_GFLOP[name] = round(swinir_flops(mk(), 126, 126)["train"] / 1e9, 2)
     elif name == "rrdbnet":
         from kair_amd.models.network_rrdbnet import RRDBNet
         mk = lambda: RRDBNet(3, 3, 64, 23, 32, 4, compute_dtype=dtype)   # noqa: E731
