@@ -35,8 +35,11 @@ typedef enum { KAIR_F32 = 0, KAIR_BF16 = 1, KAIR_F16 = 3 } kair_dtype;
  * operand in fp16's range) and every product as hi.hi + hi.lo + lo.hi with fp32 accumulation, rescaled by
  * 2^-(eA + eB): ~2^-21 relative per product, the precision class of fp32 arithmetic (one bf16 product:
  * 2^-8; bf16 pairs: 2^-16).  Operands: fp32 (split in the kernel) or fp16 hi planes with
- * kair_operand.lo_ptr (their stored values carry x3_exp).  Packed weights (kinds 9 / 17 / 18 / 19 with an
- * fp16 destination) hold w * 2^KAIR_X3_WEXP. */
+ * kair_operand.lo_ptr (their stored values carry x3_exp).  Packed weights (kinds 9 / 17 / 18 / 19 / 20 / 21 with
+ * an fp16 destination) hold w * 2^KAIR_X3_WEXP.  kair_gemm_nt's A and kair_gemm_tn's B may be the space-to-depth
+ * operand (KAIR_LD_S2D) of an fp32 map with im_C % 8 == 0, K == 4 * im_C and whole im_H x im_W grids of rows (split
+ * at the LDS commit; the 2x2 / stride-2 conv forward, the transposed conv's input gradient and both weight
+ * gradients); any other space-to-depth geometry is KAIR_ERR_ARG. */
 #define KAIR_COMPUTE_X3 2
 #define KAIR_X3_WEXP 12
 
@@ -192,7 +195,12 @@ typedef struct {
                           kair_conv3x3_wr's split form);
                         16 conv3x3 dgrad form (kind 2) in the kind-14 fragment order (bf16):
                           [Kp/16][9*Np/32][64][8], rows = input channels, k = tap*Np + cop
-                          (kair_conv3x3_wr's plain form over the output gradient, flip = 1) */
+                          (kair_conv3x3_wr's plain form over the output gradient, flip = 1);
+                        17 / 18 / 19 hi/lo pairs of kinds 0 / 2 / 3 (bf16, or x3 fp16 pairs of w 2^KAIR_X3_WEXP):
+                          each row of the plain form as 64-column chunks alternating hi / lo, row length
+                          2*ceil(rowlen/64)*64 (the layout the x3 NT kernels read, as kind 9);
+                        20 the same pair form of kind 7: rows Np of 4*Kp columns, k = tap*Kp + kp (Kp % 8 == 0);
+                        21 the same pair form of kind 8: rows kp*4 + tap of Np columns (Np % 8 == 0) */
   int N, K;          /* reference dims: linear (out,in); conv (Cout,Cin)                     */
   int nG, nGr, nGp;  /* out dim = nG groups of nGr real rows padded to nGp                   */
   int kG, kGr, kGp;  /* in  dim = kG groups of kGr real cols padded to kGp (kinds 1 / 9 only: kG*kGr

@@ -349,7 +349,8 @@ def im2col(t, H, W, C, flip=False, ones_col=-1, ld=None, up=1, ones_in_data=Fals
 
 def s2d(t, H, W, C, ld=None):
     """2x2 / stride-2 space-to-depth view of an NHWC map: H x W is the OUTPUT grid (the source is
-    2H x 2W), column k = (i*2 + j) * C + c reads pixel (2y+i, 2x+j), channel c."""
+    2H x 2W), column k = (i*2 + j) * C + c reads pixel (2y+i, 2x+j), channel c.  compute X3: an fp32 map,
+    C % 8 == 0, K = 4 C (gemm_nt A / gemm_tn B)."""
     o = Operand()
     o._keep = t
     o.ptr = ptr(t)
@@ -419,7 +420,9 @@ def epilogue(out, mode=OUT_ROWS, ldo=None, win=None, bias=None, act=ACT_NONE, sl
 
 def wmap(kind, N, K, n_groups=(1, None, None), k_groups=(1, None, None), n_perm=0):
     """n_groups = (G, real, padded) for the out dim; k_groups likewise for the in dim; n_perm = r*r
-    stores the out dim sub-pixel-major (PixelShuffle SPM layouts)."""
+    stores the out dim sub-pixel-major (PixelShuffle SPM layouts).  Kinds: kair_wmap (kair_hip.h); the x3
+    fp16-pair forms are 9 / 17 / 18 / 19 (3x3 forward, linear, 3x3 dgrad, transposed linear) and 20 / 21 (the
+    2x2 forms 7 / 8)."""
     m = WMap()
     m.kind, m.N, m.K = kind, N, K
     m.n_perm = n_perm

@@ -240,33 +240,35 @@ KAIR_DEV void pack_chunk(const float* __restrict__ src, bf16* __restrict__ dst, 
   *(bf16x8*)(dst + t0) = o;
 }
 
-// Chunked packing of the split pair forms (kinds 9, 17, 18, 19; x3 fp16 pairs of w 2^KAIR_X3_WEXP or bf16 hi / lo):
+// Chunked packing of the split pair forms (kinds 9, 17, 18, 19, 20, 21; x3 fp16 pairs of w 2^KAIR_X3_WEXP or bf16 hi / lo):
 // one thread makes 8 consecutive columns of one packed row -- its hi and lo halves, two 16-byte stores -- with 32-bit
 // index math and the row's output channel / tap resolved once (the per-element form re-derived both per element in
 // 64-bit divides, ~300 us for the classical x4 network's 47 M packed elements per step).  Row geometry: kind 9 rows
-// Np of 9 Kp (tap-major), 17 rows Np of Kp, 18 rows Kp of 9 Np (tap-major), 19 rows Kp of Np; a chunk never straddles
+// Np of 9 Kp (tap-major), 17 rows Np of Kp, 18 rows Kp of 9 Np (tap-major), 19 rows Kp of Np; the 2x2 forms: 20 (the
+// pair of kind 7) rows Np of 4 Kp (tap-major), 21 (the pair of kind 8) rows kp * 4 + tap of Np; a chunk never straddles
 // a tap (Kp / Np % 8 == 0, pack_pair_vec).
 __host__ __device__ inline bool pack_pair_vec(const kair_wmap& mp, int dt) {
   if (dt != KAIR_F16 && dt != KAIR_BF16) return false;
   const int Np = mp.nG * mp.nGp, Kp = mp.kG * mp.kGp;
-  if (mp.kind == 9 || mp.kind == 17) return Kp % 8 == 0;
-  if (mp.kind == 18 || mp.kind == 19) return Np % 8 == 0;
+  if (mp.kind == 9 || mp.kind == 17 || mp.kind == 20) return Kp % 8 == 0;
+  if (mp.kind == 18 || mp.kind == 19 || mp.kind == 21) return Np % 8 == 0;
   return false;
 }
 
 KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ dst, int dt, const kair_wmap& mp, int u) {
   const int Np = mp.nG * mp.nGp, Kp = mp.kG * mp.kGp;
-  const bool rows_n = mp.kind == 9 || mp.kind == 17;   // rows are output channels (else input channels)
-  const int rowlen = mp.kind == 9 ? 9 * Kp : mp.kind == 17 ? Kp : mp.kind == 18 ? 9 * Np : Np;
+  const bool rows_n = mp.kind == 9 || mp.kind == 17 || mp.kind == 20;   // rows are output channels (else input channels)
+  const int rowlen = mp.kind == 9 ? 9 * Kp : mp.kind == 17 ? Kp : mp.kind == 18 ? 9 * Np : mp.kind == 20 ? 4 * Kp : Np;
   const int rl64 = (rowlen + 63) / 64 * 64, cpr = rl64 / 8;
   const int row = u / cpr, k0 = (u - row * cpr) * 8;
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = 0.f;
   if (k0 < rowlen) {
-    const int rr = rows_n ? nperm_fwd(mp, unpad(row, mp.nG, mp.nGr, mp.nGp)) : unpad(row, mp.kG, mp.kGr, mp.kGp);
-    const int seg = (mp.kind == 9) ? Kp : (mp.kind == 18) ? Np : rowlen;   // tap-major forms: one tap per segment
-    const int tap = k0 / seg, c0 = k0 - tap * seg;
+    const int rr = rows_n ? nperm_fwd(mp, unpad(row, mp.nG, mp.nGr, mp.nGp))
+                          : unpad(mp.kind == 21 ? row >> 2 : row, mp.kG, mp.kGr, mp.kGp);
+    const int seg = (mp.kind == 9 || mp.kind == 20) ? Kp : (mp.kind == 18) ? Np : rowlen;   // tap-major forms: one tap per segment
+    const int tap = mp.kind == 21 ? (row & 3) : k0 / seg, c0 = mp.kind == 21 ? k0 : k0 - (k0 / seg) * seg;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = c0 + j;
@@ -276,6 +278,7 @@ KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ 
       if (n < 0 || k < 0) continue;
       if (mp.kind == 9) v[j] = src[((long)n * mp.K + k % mp.K) * 9 + tap];   // % K: tied in-dim copies
       else if (mp.kind == 18) v[j] = src[((long)n * mp.K + k) * 9 + tap];
+      else if (mp.kind == 20 || mp.kind == 21) v[j] = src[((long)n * mp.K + k) * 4 + tap];
       else v[j] = src[(long)n * mp.K + k];
     }
   }
@@ -300,6 +303,13 @@ KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ 
     *(bf16x8*)((bf16*)dst + o) = hi;
     *(bf16x8*)((bf16*)dst + o + 64) = lo;
   }
+}
+
+// one pair-chunked job on its own (kair_pack_weight of the 2x2 pair forms 20 / 21, which have no per-element form)
+__global__ __launch_bounds__(256) void pack_pair_kernel(const float* __restrict__ src, void* __restrict__ dst, int dt,
+                                                        kair_wmap mp, long chunks) {
+  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u < chunks) pack_pair_chunk(src, dst, dt, mp, (int)u);
 }
 
 // All packs of a network in one launch: table = kair_pack_job[njobs] followed by the first block
@@ -851,9 +861,9 @@ static int pack_total(const kair_wmap& mp, int dst_dtype, long* total) {
                  "pack_weight: the hi/lo split forms 12 / 15 are bf16 only");
   KAIR_CHECK_ARG(mp.kind != 9 || dst_dtype == KAIR_BF16 || dst_dtype == KAIR_F16,
                  "pack_weight: kind 9 is a bf16 or (x3) fp16 pair form");
-  KAIR_CHECK_ARG(dst_dtype == KAIR_F32 || dst_dtype == KAIR_BF16 || ((mp.kind == 9 || (mp.kind >= 17 && mp.kind <= 19)) &&
+  KAIR_CHECK_ARG(dst_dtype == KAIR_F32 || dst_dtype == KAIR_BF16 || ((mp.kind == 9 || (mp.kind >= 17 && mp.kind <= 21)) &&
                                                                      dst_dtype == KAIR_F16),
-                 "pack_weight: fp16 destinations are the x3 pair forms (kinds 9, 17, 18, 19)");
+                 "pack_weight: fp16 destinations are the x3 pair forms (kinds 9, 17, 18, 19, 20, 21)");
   KAIR_CHECK_ARG(mp.nG > 0 && mp.nGr > 0 && mp.nGp >= mp.nGr && mp.nG * mp.nGr == mp.N, "pack_weight: bad N map");
   // kinds 1 / 9 (conv forward) may repeat the in dim (kG * kGr a multiple of K: tied copies, e.g. the
   // hi / lo halves of a split input image); every other kind maps it one to one
@@ -878,6 +888,14 @@ static int pack_total(const kair_wmap& mp, int dst_dtype, long* total) {
     *total = rows * 2 * ((rowlen + 63) / 64) * 64;
     return 0;
   }
+  if (mp.kind == 20 || mp.kind == 21) {   // hi/lo split rows of the 2x2 forms 7 / 8: the chunked packer only
+    KAIR_CHECK_ARG(dst_dtype == KAIR_BF16 || dst_dtype == KAIR_F16, "pack_weight: kinds 20 / 21 are bf16 / fp16 pairs");
+    KAIR_CHECK_ARG(pack_pair_vec(mp, dst_dtype), "pack_weight: kind 20 needs Kp %% 8 == 0, kind 21 Np %% 8 == 0");
+    const long rows = mp.kind == 20 ? Np : 4 * Kp, rowlen = mp.kind == 20 ? 4 * Kp : Np;
+    KAIR_CHECK_ARG(rows * ((rowlen + 63) / 64 * 8) < (1L << 31), "pack_weight: kind %d pack too large", mp.kind);
+    *total = rows * 2 * ((rowlen + 63) / 64) * 64;
+    return 0;
+  }
   if (mp.kind == 0 || mp.kind == 3 || mp.kind == 10 || mp.kind == 13 || mp.kind == 14) *total = Np * Kp;
   else if (mp.kind == 12) *total = 2 * Np * Kp;
   else if (mp.kind == 1 || mp.kind == 2 || mp.kind == 16) *total = Np * 9 * Kp;
@@ -893,6 +911,12 @@ extern "C" int kair_pack_weight(const float* src, void* dst, int dst_dtype, cons
   KAIR_CHECK_ARG(src && dst && map, "pack_weight: null pointer");
   long total;
   if (int rc = pack_total(*map, dst_dtype, &total)) return rc;
+  if (map->kind == 20 || map->kind == 21) {
+    KAIR_LAUNCH(pack_pair_kernel, dim3(nblk(total / 16, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, dst_dtype,
+                       *map, total / 16);
+    KAIR_CHECK_LAUNCH();
+    return 0;
+  }
   KAIR_LAUNCH(pack_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, dst_dtype, *map,
                      total);
   KAIR_CHECK_LAUNCH();

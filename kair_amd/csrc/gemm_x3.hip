@@ -65,7 +65,8 @@ KAIR_DEV f16x8 trfrag(const f16* base, int ld) {
 template <typename TA, int AM, int BM, int BN>
 __global__ __launch_bounds__(NT, 2) void gemm_nt_x3_kernel(Op A, Op B, Epi E, int K, int tilesN, int nwg) {
   constexpr int BK = 32, LD = BK + 8;
-  constexpr int WM = 2, WN = 2, TM = BM / WM, TN = BN / WN, RM = TM / 16, RN = TN / 16;
+  constexpr int WN = BN >= 32 ? 2 : 1, WM = 4 / WN;   // a 16-column tile: the four waves down the rows
+  constexpr int TM = BM / WM, TN = BN / WN, RM = TM / 16, RN = TN / 16;
   constexpr int CPR = BK / 8;
   constexpr int CA = BM * CPR, CB = BN * CPR;
   constexpr int PA = (CA + NT - 1) / NT, PB = (CB + NT - 1) / NT;
@@ -1264,10 +1265,20 @@ int launch_nt_x3(const Op& A, const Op& B, const Epi& E, long M, int N, int K, h
   return 0;
 }
 
-// tile: 32 / 64 / 128 columns by N; 128 rows, 64 when that leaves fewer than two workgroups per CU
+// KAIR_X3_NARROW=0 turns the narrow tiles off (A/B: profiles/usrnet_x3_narrow_ab.txt): the 16-column NT tile and the
+// 32 x 160 / 64 x 128 TN tiles, the x3 forms of gemm.hip's narrow tiles (nt_tiles, tn_narrow_shape / tn_narrow64_shape)
+bool x3_narrow() {
+  static const bool on = [] { const char* e = getenv("KAIR_X3_NARROW"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
+// tile: 16 / 32 / 64 / 128 columns by N; 128 rows, 64 when that leaves fewer than two workgroups per CU
 template <typename TA, int AM>
 int nt_x3_tiles(const Op& A, const Op& B, const Epi& E, long M, int N, int K, hipStream_t s) {
   const long min_wg = 2L * x3_cus();
+  // fp32 A, N <= 16 (the ResUNet's 16-channel level, 8-column heads / tails): no half-empty 32-column tile
+  if constexpr (sizeof(TA) == 4)
+    if (N <= 16 && x3_narrow()) return launch_nt_x3<TA, AM, 128, 16>(A, B, E, M, N, K, s);
   if (N <= 32) return launch_nt_x3<TA, AM, 128, 32>(A, B, E, M, N, K, s);
   if (N <= 64) {
     if ((M + 127) / 128 >= min_wg) return launch_nt_x3<TA, AM, 128, 64>(A, B, E, M, N, K, s);
@@ -1280,9 +1291,22 @@ int nt_x3_tiles(const Op& A, const Op& B, const Epi& E, long M, int N, int K, hi
 template <typename TA, typename TB, int AMB>
 int launch_tn_x3(const Op& a, const Op& b, float* ws, int splits, long M, int N, int K, long rps, float acc_scale,
                  hipStream_t s) {
+  constexpr bool f32 = sizeof(TA) == 4 && sizeof(TB) == 4;   // the narrow tiles: fp32 operands (the conv engines')
   if (N <= 64 && K <= 64) {
     KAIR_LAUNCH((gemm_tn_x3_kernel<TA, TB, AMB, 64, 64>), dim3(1, splits), dim3(NT), 0, s, a, b, ws, M, N, K, rps, 1,
                        acc_scale);
+  } else if (f32 && N <= 32 && x3_narrow()) {   // a 128 x 128 tile would be >= 3/4 empty along N
+    if constexpr (f32) {
+      const int tilesK = (K + 159) / 160;
+      KAIR_LAUNCH((gemm_tn_x3_kernel<TA, TB, AMB, 32, 160>), dim3(tilesK, splits), dim3(NT), 0, s, a, b, ws, M, N, K, rps,
+                         tilesK, acc_scale);
+    }
+  } else if (f32 && N <= 64 && x3_narrow()) {   // ... half empty
+    if constexpr (f32) {
+      const int tilesK = (K + 127) / 128;
+      KAIR_LAUNCH((gemm_tn_x3_kernel<TA, TB, AMB, 64, 128>), dim3(tilesK, splits), dim3(NT), 0, s, a, b, ws, M, N, K, rps,
+                         tilesK, acc_scale);
+    }
   } else {
     const int tilesN = (N + 127) / 128, tilesK = (K + 127) / 128;
     KAIR_LAUNCH((gemm_tn_x3_kernel<TA, TB, AMB, 128, 128>), dim3(tilesN * tilesK, splits), dim3(NT), 0, s, a, b, ws,
@@ -1298,6 +1322,8 @@ int tn_x3_b(const Op& a, const Op& b, int bmode, int bdt, float* ws, int splits,
   if (bmode == KAIR_LD_ROWS)
     return bdt == KAIR_F16 ? launch_tn_x3<TA, f16, AM_ROWS>(a, b, ws, splits, M, N, K, rps, acc_scale, s)
                            : launch_tn_x3<TA, float, AM_ROWS>(a, b, ws, splits, M, N, K, rps, acc_scale, s);
+  if (bmode == KAIR_LD_S2D)   // fp32 maps only (kair_gemm_tn_x3 checks)
+    return launch_tn_x3<TA, float, AM_S2D>(a, b, ws, splits, M, N, K, rps, acc_scale, s);
   return bdt == KAIR_F16 ? launch_tn_x3<TA, f16, AM_IM2COL>(a, b, ws, splits, M, N, K, rps, acc_scale, s)
                          : launch_tn_x3<TA, float, AM_IM2COL>(a, b, ws, splits, M, N, K, rps, acc_scale, s);
 }
@@ -1449,6 +1475,17 @@ int x3_operand_ok(const kair_operand* o, const char* what) {
   return 0;
 }
 
+// the space-to-depth operand of the 2x2 / stride-2 forms: an fp32 NHWC map of whole [2 im_H, 2 im_W] images, im_C % 8
+// channels (a chunk of 8 columns stays inside one tap), K = the four taps
+int x3_s2d_ok(const kair_operand* o, long M, int K, const char* what) {
+  KAIR_CHECK_ARG(o->dtype == KAIR_F32, "%s: the x3 space-to-depth operand is an fp32 map", what);
+  KAIR_CHECK_ARG(o->im_C > 0 && o->im_C % 8 == 0 && o->im_H > 0 && o->im_W > 0 && K == 4 * o->im_C,
+                 "%s: space-to-depth needs im_C %% 8 == 0 and K == 4 * im_C (im_C %d, K %d)", what, o->im_C, K);
+  KAIR_CHECK_ARG(M % ((long)o->im_H * o->im_W) == 0, "%s: space-to-depth rows must be whole im_H x im_W grids", what);
+  KAIR_CHECK_ARG(!o->rowscale && o->ones_col < 0 && o->win_ws == 0, "%s: no row scale / ones column / window map", what);
+  return 0;
+}
+
 }  // namespace
 
 // every job fp16 pairs in rows, 16-byte aligned 8-column units, no window map (tn_x3_ring_ok's pair branch)
@@ -1508,7 +1545,9 @@ int kair_gemm_nt_x3(const kair_operand* A, const kair_operand* B, const kair_epi
   int rc;
   if ((rc = x3_operand_ok(A, "gemm_nt x3 A"))) return rc;
   KAIR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0, "gemm_nt x3: bad M/N/K (%ld,%d,%d)", M, N, K);
-  KAIR_CHECK_ARG(A->mode == KAIR_LD_ROWS || A->mode == KAIR_LD_IM2COL3, "gemm_nt x3: A rows or im2col");
+  KAIR_CHECK_ARG(A->mode == KAIR_LD_ROWS || A->mode == KAIR_LD_IM2COL3 || A->mode == KAIR_LD_S2D,
+                 "gemm_nt x3: A rows, im2col or space-to-depth");
+  if (A->mode == KAIR_LD_S2D && (rc = x3_s2d_ok(A, M, K, "gemm_nt x3 A"))) return rc;
   KAIR_CHECK_ARG(A->ones_col < 0 && !A->rowscale, "gemm_nt x3: no ones column / row scale on A");
   KAIR_CHECK_ARG(B->mode == KAIR_LD_ROWS && B->dtype == KAIR_F16 && B->win_ws == 0 && B->ld >= 2L * ((K + 63) / 64) * 64 &&
                      B->ld % 8 == 0,
@@ -1532,6 +1571,7 @@ int kair_gemm_nt_x3(const kair_operand* A, const kair_operand* B, const kair_epi
     return A->dtype == KAIR_F16 ? nt_x3_ring_dispatch<f16, AM_ROWS>(a, b, e, M, N, K, s)
                                 : nt_x3_ring_dispatch<float, AM_ROWS>(a, b, e, M, N, K, s);
   }
+  if (A->mode == KAIR_LD_S2D) return nt_x3_tiles<float, AM_S2D>(a, b, e, M, N, K, s);   // never a ring shape (nt_x3_ring_ok)
   if (A->dtype == KAIR_F16)
     return A->mode == KAIR_LD_ROWS ? nt_x3_tiles<f16, AM_ROWS>(a, b, e, M, N, K, s) : nt_x3_tiles<f16, AM_IM2COL>(a, b, e, M, N, K, s);
   return A->mode == KAIR_LD_ROWS ? nt_x3_tiles<float, AM_ROWS>(a, b, e, M, N, K, s) : nt_x3_tiles<float, AM_IM2COL>(a, b, e, M, N, K, s);
@@ -1586,8 +1626,9 @@ int kair_gemm_tn_x3(const kair_operand* A, const kair_operand* B, float* ws, int
   int rc;
   if ((rc = x3_operand_ok(A, "gemm_tn x3 A"))) return rc;
   if ((rc = x3_operand_ok(B, "gemm_tn x3 B"))) return rc;
-  KAIR_CHECK_ARG(A->mode == KAIR_LD_ROWS && (B->mode == KAIR_LD_ROWS || B->mode == KAIR_LD_IM2COL3),
-                 "gemm_tn x3: A rows, B rows or im2col");
+  KAIR_CHECK_ARG(A->mode == KAIR_LD_ROWS && (B->mode == KAIR_LD_ROWS || B->mode == KAIR_LD_IM2COL3 || B->mode == KAIR_LD_S2D),
+                 "gemm_tn x3: A rows, B rows, im2col or space-to-depth");
+  if (B->mode == KAIR_LD_S2D && (rc = x3_s2d_ok(B, M, K, "gemm_tn x3 B"))) return rc;
   KAIR_CHECK_ARG(M < KAIR_MAX_MAPPED_ROWS && N < KAIR_MAX_MAPPED_ROWS && K < KAIR_MAX_MAPPED_ROWS,
                  "gemm_tn x3: dimensions must be < 2^24");
   const Op a = make_op(*A, M), b = make_op(*B, M);

@@ -26,6 +26,7 @@ the replicate-padded grid (v1:148-151) and crops its output (v1:164) -- kair_usr
 (crop adjoint) of the output gradient and the fold (replicate adjoint) of the input gradient in
 backward.  B*Hp*Wp < 2^24.
 """
+import math
 import weakref
 
 import torch
@@ -35,6 +36,11 @@ from .. import _hip as H
 from .plans import Lease, PlanPool, autograd_mode, plan_mode
 
 C8 = 8   # channel stride of the ResUNet input (x, beta) and of the tail-output gradient rows
+
+
+def _ks(k):
+    """Row length of a split-pair pack of k columns: 64-column chunks alternating hi / lo."""
+    return 2 * (-(-k // 64)) * 64
 
 
 def _mods(m):
@@ -48,51 +54,69 @@ class _Conv3:
         self.w = mod.weight
         self.Co, self.Ci = self.w.shape[:2]
         self.Cop, self.Cip = Cop or self.Co, Cip or self.Ci
-        self.map = H.wmap(1, self.Co, self.Ci, (1, self.Co, self.Cop), (1, self.Ci, self.Cip))
-        self.mapd = H.wmap(2, self.Co, self.Ci, (1, self.Co, self.Cop), (1, self.Ci, self.Cip))
-        self.Wf = eng._e(self.Cop, 9 * self.Cip, dt=eng.tdt)
-        self.Wd = eng._e(self.Cip, 9 * self.Cop, dt=eng.tdt)
+        grp = ((1, self.Co, self.Cop), (1, self.Ci, self.Cip))
+        self.map = H.wmap(1, self.Co, self.Ci, *grp)      # the weight gradient's layout (wgrad_finalize)
+        if eng.x3:   # fp16 pairs of w 2^X3_WEXP: kinds 9 / 18
+            self.mapf, self.mapd = H.wmap(9, self.Co, self.Ci, *grp), H.wmap(18, self.Co, self.Ci, *grp)
+            self.Wf = eng._e(self.Cop, _ks(9 * self.Cip), dt=torch.float16)
+            self.Wd = eng._e(self.Cip, _ks(9 * self.Cop), dt=torch.float16)
+        else:
+            self.mapf, self.mapd = self.map, H.wmap(2, self.Co, self.Ci, *grp)
+            self.Wf = eng._e(self.Cop, 9 * self.Cip, dt=eng.tdt)
+            self.Wd = eng._e(self.Cip, 9 * self.Cop, dt=eng.tdt)
 
     def pack_jobs(self):
         w = self.w.detach()
-        return [(w, self.Wf, self.map), (w, self.Wd, self.mapd)]
+        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
 
 
 class _Down:
     """Conv2d(Ci, Co, 2, stride 2, bias=False) (basicblock.downsample_strideconv, basicblock.py:495-501):
     forward through the space-to-depth operand with the [Co][4 Ci] pack (kind 7); input gradient as a
-    1x1 GEMM into a pixel-shuffle store with the [4 Ci][Co] pack (kind 8); weight gradient kind 7."""
+    1x1 GEMM into a pixel-shuffle store with the [4 Ci][Co] pack (kind 8); weight gradient kind 7.
+    fp32x3: the fp16-pair forms of both packs (kinds 20 / 21)."""
 
     def __init__(self, eng, mod):
         self.w = mod.weight
         self.Co, self.Ci = self.w.shape[:2]
         self.map = H.wmap(7, self.Co, self.Ci)
-        self.mapd = H.wmap(8, self.Co, self.Ci)
-        self.Wf = eng._e(self.Co, 4 * self.Ci, dt=eng.tdt)
-        self.Wd = eng._e(4 * self.Ci, self.Co, dt=eng.tdt)
+        if eng.x3:
+            self.mapf, self.mapd = H.wmap(20, self.Co, self.Ci), H.wmap(21, self.Co, self.Ci)
+            self.Wf = eng._e(self.Co, _ks(4 * self.Ci), dt=torch.float16)
+            self.Wd = eng._e(4 * self.Ci, _ks(self.Co), dt=torch.float16)
+        else:
+            self.mapf, self.mapd = self.map, H.wmap(8, self.Co, self.Ci)
+            self.Wf = eng._e(self.Co, 4 * self.Ci, dt=eng.tdt)
+            self.Wd = eng._e(4 * self.Ci, self.Co, dt=eng.tdt)
 
     def pack_jobs(self):
         w = self.w.detach()
-        return [(w, self.Wf, self.map), (w, self.Wd, self.mapd)]
+        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
 
 
 class _Up:
     """ConvTranspose2d(Ci, Co, 2, stride 2, bias=False) (basicblock.upsample_convtranspose,
     basicblock.py:471-477), weight [Ci][Co][2][2]: forward as a 1x1 GEMM into a pixel-shuffle store
     with the [4 Co][Ci] pack (kind 8 over (Ci, Co)); input gradient through the space-to-depth operand
-    with the [Ci][4 Co] pack (kind 7 over (Ci, Co)); weight gradient kind 7 over (Ci, Co)."""
+    with the [Ci][4 Co] pack (kind 7 over (Ci, Co)); weight gradient kind 7 over (Ci, Co).
+    fp32x3: the fp16-pair forms of both packs (kinds 21 / 20)."""
 
     def __init__(self, eng, mod):
         self.w = mod.weight
         self.Ci, self.Co = self.w.shape[:2]
-        self.mapf = H.wmap(8, self.Ci, self.Co)
         self.map = H.wmap(7, self.Ci, self.Co)
-        self.Wf = eng._e(4 * self.Co, self.Ci, dt=eng.tdt)
-        self.Wd = eng._e(self.Ci, 4 * self.Co, dt=eng.tdt)
+        if eng.x3:
+            self.mapf, self.mapd = H.wmap(21, self.Ci, self.Co), H.wmap(20, self.Ci, self.Co)
+            self.Wf = eng._e(4 * self.Co, _ks(self.Ci), dt=torch.float16)
+            self.Wd = eng._e(self.Ci, _ks(4 * self.Co), dt=torch.float16)
+        else:
+            self.mapf, self.mapd = H.wmap(8, self.Ci, self.Co), self.map
+            self.Wf = eng._e(4 * self.Co, self.Ci, dt=eng.tdt)
+            self.Wd = eng._e(self.Ci, 4 * self.Co, dt=eng.tdt)
 
     def pack_jobs(self):
         w = self.w.detach()
-        return [(w, self.Wf, self.mapf), (w, self.Wd, self.map)]
+        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
 
 
 class _RB:
@@ -103,10 +127,19 @@ class _RB:
 class USRNetEngine:
     def __init__(self, net, compute_dtype="bf16"):
         self.net_ref = weakref.ref(net)
-        if compute_dtype not in ("bf16", "fp32"):
+        if compute_dtype not in ("bf16", "fp32", "fp32x3"):
             raise ValueError(compute_dtype)
+        # fp32x3 (the reference's fp32 precision class on the 16-bit matrix cores, as RRDBNetEngine): fp32 maps and
+        # gradients in HBM, every ResUNet product as hi.hi + hi.lo + lo.hi of power-of-2-scaled fp16 pairs (split in
+        # the GEMM kernels, weights packed as fp16 pairs), fp32 accumulation; the FFT / DataNet / HyPaNet passes are
+        # the fp32 engine's.  cd stays F32, the launches go through _nt / _wgrad with compute KAIR_COMPUTE_X3
+        self.x3 = compute_dtype == "fp32x3"
         self.cd = H.BF16 if compute_dtype == "bf16" else H.F32
         self.tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        self.X3_AEXP = 4          # activation exponent (lowered by x3_backoff)
+        self.x3_gexp_off = 4      # gradient exponent over the loss normalisation
+        self.x3_backoffs = 0
+        self._ax = self.X3_AEXP   # the exponent of the GEMM A operands of the phase being issued
         p = net.p
         self.device = p.m_head.weight.device
         self.n = net.n
@@ -141,6 +174,36 @@ class USRNetEngine:
 
     def _e(self, *shape, dt=torch.float32):
         return torch.empty(*shape, device=self.device, dtype=dt)
+
+    X3_BACKOFF_STEP, X3_BACKOFF_MAX = 6, 4
+
+    def _nt(self, A, B, E, M, N, K):
+        """kair_gemm_nt in the engine's arithmetic; fp32x3: A carries the phase exponent, B the weight packs'."""
+        if self.x3:
+            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
+            H.gemm_nt(A, B, E, M, N, K, H.X3)
+        else:
+            H.gemm_nt(A, B, E, M, N, K, self.cd)
+
+    def _x3_grad_exp(self, numel, weight=1.0):
+        """Data gradients of a mean loss are O(weight / numel): times 2^(log2(numel / weight) + 4) they sit near 2^4."""
+        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
+
+    def x3_backoff(self, step=None, act=True, grad=True):
+        """The range guard's reaction (FusedTrainer.check_range; RRDBNetEngine.x3_backoff)."""
+        if not self.x3:
+            raise RuntimeError("x3_backoff: not an fp32x3 engine")
+        if self.x3_backoffs >= self.X3_BACKOFF_MAX:
+            raise RuntimeError(f"fp32x3 range guard: the step is still non-finite after {self.x3_backoffs} exponent "
+                               f"back-offs: the data is not finite, or a weight left its pack window |w| < "
+                               f"2^{16 - H.X3_WEXP}")
+        step = self.X3_BACKOFF_STEP if step is None else int(step)
+        if act:
+            self.X3_AEXP -= step
+        if grad:
+            self.x3_gexp_off -= step
+        self.x3_backoffs += 1
+        return self.X3_AEXP, self.x3_gexp_off
 
     def convs(self):
         cs = [self.head, self.tail] + self.downs + self.ups
@@ -229,6 +292,7 @@ class USRNetEngine:
         P = self.plan(B, h, w, sf, kh, kw)
         self.pack()
         self.cur = P
+        self._ax = self.X3_AEXP   # fp32x3: forward operands are activations
         x = x.contiguous().float()
         k = k.contiguous().float()
         P["x_in"], P["k_in"] = x, k
@@ -268,40 +332,40 @@ class USRNetEngine:
 
     def _chain_fwd(self, rbs, bufs, x, Hl, Wl, M, c, skip=None):
         """ResBlocks x + conv2(relu(conv1(x))); the last adds `skip` (the U-Net skip) too."""
-        cd, cur = self.cd, x
+        cur = x
         for j, (rb, S) in enumerate(zip(rbs, bufs)):
-            H.gemm_nt(H.im2col(cur, Hl, Wl, c), H.rows(rb.c1.Wf), H.epilogue(S["h"], act=H.ACT_RELU), M, c, 9 * c, cd)
+            self._nt(H.im2col(cur, Hl, Wl, c), H.rows(rb.c1.Wf), H.epilogue(S["h"], act=H.ACT_RELU), M, c, 9 * c)
             last = j == len(rbs) - 1
-            H.gemm_nt(H.im2col(S["h"], Hl, Wl, c), H.rows(rb.c2.Wf),
-                      H.epilogue(S["out"], resid=cur, resid2=skip if last else None), M, c, 9 * c, cd)
+            self._nt(H.im2col(S["h"], Hl, Wl, c), H.rows(rb.c2.Wf),
+                     H.epilogue(S["out"], resid=cur, resid2=skip if last else None), M, c, 9 * c)
             cur = S["out"]
         return cur
 
     def _unet_fwd(self, P, S):
-        cd, nc, M = self.cd, self.nc, P["M"]
+        nc, M = self.nc, P["M"]
         H0, W0 = self._grid(P, 0)
-        H.gemm_nt(H.im2col(S["xin"], H0, W0, C8), H.rows(self.head.Wf), H.epilogue(S["X"][0]), M[0], nc[0], 9 * C8, cd)
+        self._nt(H.im2col(S["xin"], H0, W0, C8), H.rows(self.head.Wf), H.epilogue(S["X"][0]), M[0], nc[0], 9 * C8)
         cur = S["X"][0]
         for l in range(3):
             Hl, Wl = self._grid(P, l)
             a = self._chain_fwd(self.down_rbs[l], S["down"][l], cur, Hl, Wl, M[l], nc[l])
             Hn, Wn = self._grid(P, l + 1)
-            H.gemm_nt(H.s2d(a, Hn, Wn, nc[l]), H.rows(self.downs[l].Wf), H.epilogue(S["X"][l + 1]), M[l + 1], nc[l + 1],
-                      4 * nc[l], cd)
+            self._nt(H.s2d(a, Hn, Wn, nc[l]), H.rows(self.downs[l].Wf), H.epilogue(S["X"][l + 1]), M[l + 1], nc[l + 1],
+                     4 * nc[l])
             cur = S["X"][l + 1]
         H3, W3 = self._grid(P, 3)
         s = self._chain_fwd(self.body_rbs, S["body"], cur, H3, W3, M[3], nc[3], skip=S["X"][3])
         for u in range(3):
             l = 2 - u                              # output level of m_up(3-u)
             Hs, Ws = self._grid(P, l + 1)
-            H.gemm_nt(H.rows(s), H.rows(self.ups[u].Wf), H.epilogue(S["t"][l], mode=H.OUT_PSHUF, ldo=nc[l], ps=(2, Hs, Ws)),
-                      M[l + 1], 4 * nc[l], nc[l + 1], cd)
+            self._nt(H.rows(s), H.rows(self.ups[u].Wf), H.epilogue(S["t"][l], mode=H.OUT_PSHUF, ldo=nc[l], ps=(2, Hs, Ws)),
+                     M[l + 1], 4 * nc[l], nc[l + 1])
             Hl, Wl = self._grid(P, l)
             s = self._chain_fwd(self.up_rbs[u], S["up"][l], S["t"][l], Hl, Wl, M[l], nc[l], skip=S["X"][l])
         xo = S["xout_p"] if P["pad"] else S["xout"]
-        H.gemm_nt(H.im2col(s, H0, W0, nc[0]), H.rows(self.tail.Wf),
-                  H.epilogue(xo, mode=H.OUT_NCHW, ldo=0, img=(None, 1.0, self.out_nc, H0, W0)), M[0], C8,
-                  9 * nc[0], cd)
+        self._nt(H.im2col(s, H0, W0, nc[0]), H.rows(self.tail.Wf),
+                 H.epilogue(xo, mode=H.OUT_NCHW, ldo=0, img=(None, 1.0, self.out_nc, H0, W0)), M[0], C8,
+                 9 * nc[0])
         if P["pad"]:   # x[..., :h, :w] (v1:164)
             H.usr_pad(xo, S["xout"], H.USR_CROP_NCHW, 0, P["B"] * self.out_nc, P["H"], P["W"], H0, W0)
 
@@ -312,18 +376,25 @@ class USRNetEngine:
         P = self.cur
         H.l1_loss(P["it"][-1]["xout"], H_img, P["loss"], P["gE"], C8, loss_weight, P["B"], self.out_nc, P["H"], P["W"],
                   P["loss_ws"], charb_eps=charb_eps)
+        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_nc * P["H"] * P["W"], loss_weight)
         self.backward(grads, P)
         return P["loss"]
 
     def backward_from_grad(self, gE, grads):
         P = self.cur
         H.image_to_nhwc(gE.contiguous(), P["gE"], C8, None, 1.0, P["B"], self.out_nc, P["H"], P["W"])
+        if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
+            mx = float(gE.abs().max())
+            P["e_g"] = (8 - int(math.ceil(math.log2(mx)))) if mx > 0 and math.isfinite(mx) else 0
         self.backward(grads, P)
 
     def backward(self, grads, P):
         B, C, Hh, Ww, sf, n = P["B"], self.out_nc, P["H"], P["W"], P["sf"], self.n
         planes, inv_n = B * C, 1.0 / (Hh * Ww)
         ab, gab = P["ab"], P["gab"]
+        # fp32x3: backward GEMM A operands are data gradients.  One exponent serves every stage (measured at
+        # n_iter = 6, DESIGN.md 3a "USRNet": the bars hold with two orders of magnitude to spare)
+        self._ax = P.get("e_g", 0)
         for i in range(n - 1, -1, -1):
             S = P["it"][i]
             self._unet_bwd(P, S, grads, acc=i < n - 1)
@@ -343,36 +414,40 @@ class USRNetEngine:
         hp = self._hyp()
         H.hypanet_bwd(P["sig"], float(sf), *hp, self.hc, self.no, B, gab, *[grads[t] for t in hp])
 
-    def _wgrad(self, P, A, Bop, M, N, K, m, grad, acc):
+    def _wgrad(self, P, A, Bop, M, N, K, m, grad, acc, act_rows=False):
+        """fp32x3: (gradient, activation) operands, or (activation, gradient) with act_rows (the transposed conv)."""
         S = H.wgrad_splits(M, N, K)
-        H.gemm_tn(A, Bop, P["wg_ws"], S, M, N, K, self.cd)
+        if self.x3:
+            eg, ea = P.get("e_g", 0), self.X3_AEXP
+            A.x3_exp, Bop.x3_exp = (ea, eg) if act_rows else (eg, ea)
+        H.gemm_tn(A, Bop, P["wg_ws"], S, M, N, K, H.X3 if self.x3 else self.cd)
         H.wgrad_finalize(P["wg_ws"], S, m, grad, accumulate=acc)
 
     def _chain_bwd(self, P, rbs, bufs, x_in, g, Hl, Wl, M, c, G, grads, acc, skip_g=None):
         """g: fp32 dL/d(chain output) -> returns fp32 dL/d(chain input) (+ skip_g, the U-Net skip)."""
-        cd, cur = self.cd, g
+        cur = g
         for j in range(len(rbs) - 1, -1, -1):
             rb, S = rbs[j], bufs[j]
             r_in = bufs[j - 1]["out"] if j > 0 else x_in
-            H.gemm_nt(H.im2col(cur, Hl, Wl, c, flip=True), H.rows(rb.c2.Wd), H.epilogue(G["gz"], gate=S["h"], gate_kind=3),
-                      M, c, 9 * c, cd)
+            self._nt(H.im2col(cur, Hl, Wl, c, flip=True), H.rows(rb.c2.Wd), H.epilogue(G["gz"], gate=S["h"], gate_kind=3),
+                     M, c, 9 * c)
             self._wgrad(P, H.rows(cur), H.im2col(S["h"], Hl, Wl, c), M, c, 9 * c, rb.c2.map, grads[rb.c2.w], acc)
             out = G["ga"] if cur is not G["ga"] else G["gb"]
-            H.gemm_nt(H.im2col(G["gz"], Hl, Wl, c, flip=True), H.rows(rb.c1.Wd),
-                      H.epilogue(out, resid=cur, resid2=skip_g if j == 0 else None), M, c, 9 * c, cd)
+            self._nt(H.im2col(G["gz"], Hl, Wl, c, flip=True), H.rows(rb.c1.Wd),
+                     H.epilogue(out, resid=cur, resid2=skip_g if j == 0 else None), M, c, 9 * c)
             self._wgrad(P, H.rows(G["gz"]), H.im2col(r_in, Hl, Wl, c), M, c, 9 * c, rb.c1.map, grads[rb.c1.w], acc)
             cur = out
         return cur
 
     def _unet_bwd(self, P, S, grads, acc):
-        cd, nc, M, Gs = self.cd, self.nc, P["M"], P["G"]
+        nc, M, Gs = self.nc, P["M"], P["G"]
         H0, W0 = self._grid(P, 0)
         gE = P["gE"]
         if P["pad"]:   # adjoint of the crop: the output gradient on the padded grid, zeros outside
             H.usr_pad(gE, P["gE_p"], H.USR_PAD_ZERO, C8, P["B"], P["H"], P["W"], H0, W0)
             gE = P["gE_p"]
-        H.gemm_nt(H.im2col(gE, H0, W0, C8, flip=True), H.rows(self.tail.Wd), H.epilogue(Gs[0]["gS"]), M[0], nc[0],
-                  9 * C8, cd)
+        self._nt(H.im2col(gE, H0, W0, C8, flip=True), H.rows(self.tail.Wd), H.epilogue(Gs[0]["gS"]), M[0], nc[0],
+                 9 * C8)
         s1 = S["up"][0][-1]["out"]
         self._wgrad(P, H.rows(gE), H.im2col(s1, H0, W0, nc[0]), M[0], C8, 9 * nc[0], self.tail.map, grads[self.tail.w],
                     acc)
@@ -384,10 +459,10 @@ class USRNetEngine:
             up = self.ups[u]
             Hs, Ws = self._grid(P, l + 1)
             s_next = S["body"][-1]["out"] if l == 2 else S["up"][l + 1][-1]["out"]
-            H.gemm_nt(H.s2d(gt, Hs, Ws, nc[l]), H.rows(up.Wd), H.epilogue(Gs[l + 1]["gS"]), M[l + 1], nc[l + 1],
-                      4 * nc[l], cd)
+            self._nt(H.s2d(gt, Hs, Ws, nc[l]), H.rows(up.Wd), H.epilogue(Gs[l + 1]["gS"]), M[l + 1], nc[l + 1],
+                     4 * nc[l])
             self._wgrad(P, H.rows(s_next), H.s2d(gt, Hs, Ws, nc[l]), M[l + 1], nc[l + 1], 4 * nc[l], up.map,
-                        grads[up.w], acc)
+                        grads[up.w], acc, act_rows=True)
             g = Gs[l + 1]["gS"]
         H3, W3 = self._grid(P, 3)
         gx = self._chain_bwd(P, self.body_rbs, S["body"], S["X"][3], Gs[3]["gS"], H3, W3, M[3], nc[3], Gs[3], grads, acc,
@@ -397,13 +472,13 @@ class USRNetEngine:
             Hn, Wn = self._grid(P, l + 1)
             Hl, Wl = self._grid(P, l)
             a = S["down"][l][-1]["out"]
-            H.gemm_nt(H.rows(gx), H.rows(d.Wd), H.epilogue(Gs[l]["gc"], mode=H.OUT_PSHUF, ldo=nc[l], ps=(2, Hn, Wn)),
-                      M[l + 1], 4 * nc[l], nc[l + 1], cd)
+            self._nt(H.rows(gx), H.rows(d.Wd), H.epilogue(Gs[l]["gc"], mode=H.OUT_PSHUF, ldo=nc[l], ps=(2, Hn, Wn)),
+                     M[l + 1], 4 * nc[l], nc[l + 1])
             self._wgrad(P, H.rows(gx), H.s2d(a, Hn, Wn, nc[l]), M[l + 1], nc[l + 1], 4 * nc[l], d.map, grads[d.w], acc)
             gx = self._chain_bwd(P, self.down_rbs[l], S["down"][l], S["X"][l], Gs[l]["gc"], Hl, Wl, M[l], nc[l], Gs[l],
                                  grads, acc, skip_g=Gs[l]["gS"])
-        H.gemm_nt(H.im2col(gx, H0, W0, nc[0], flip=True), H.rows(self.head.Wd), H.epilogue(P["gxin"]), M[0], C8,
-                  9 * nc[0], cd)
+        self._nt(H.im2col(gx, H0, W0, nc[0], flip=True), H.rows(self.head.Wd), H.epilogue(P["gxin"]), M[0], C8,
+                 9 * nc[0])
         self._wgrad(P, H.rows(gx), H.im2col(S["xin"], H0, W0, C8), M[0], nc[0], 9 * C8, self.head.map,
                     grads[self.head.w], acc)
 

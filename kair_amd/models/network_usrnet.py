@@ -68,7 +68,8 @@ class HyPaNet(nn.Module):
 
 class USRNet(nn.Module):
     """network_usrnet_v1.py:228-262 (same constructor signature; compute_dtype is the engine option:
-    'bf16' MFMA operands with fp32 accumulation, or 'fp32' exact-MFMA parity mode)."""
+    'bf16' MFMA operands with fp32 accumulation, 'fp32' exact-MFMA parity mode, or 'fp32x3': the ResUNet's
+    products as three fp16-pair MFMA products, the fp32 precision class on the 16-bit matrix cores)."""
 
     def __init__(self, n_iter=8, h_nc=64, in_nc=4, out_nc=3, nc=(64, 128, 256, 512), nb=2, act_mode="R",
                  downsample_mode="strideconv", upsample_mode="convtranspose", compute_dtype="fp32"):

@@ -57,7 +57,8 @@ def define_G(opt):
     return net
 
 
-_X3_NETS = ("swinir", "rrdbnet", "rrdb")   # networks with a split-fp16 (fp32x3) engine
+_X3_NETS = ("swinir", "rrdbnet", "rrdb", "usrnet")   # networks with a split-fp16 (fp32x3) engine
+_X3_DEFAULT_NETS = ("swinir", "rrdbnet", "rrdb")     # ... whose fp32 option files get it by default
 
 
 def compute_dtype_of(opt):
@@ -69,11 +70,13 @@ def compute_dtype_of(opt):
                                             (fp32 master weights / accumulation; bf16 keeps fp32's exponent
                                             range, so no loss scaling and no {iter}_scaler.pth);
       otherwise                             the reference's default fp32 arithmetic: 'fp32x3' where the
-                                            network has that engine (SwinIR: every product on the 16-bit
+                                            network has that engine by default (SwinIR: every product on the 16-bit
                                             matrix cores as three fp16 products of power-of-2-scaled hi/lo
                                             pairs, ~2^-21 relative -- it passes the exact-fp32 engine's oracle
                                             bars, tests/test_x3_gpu.py; RRDBNet / RRDB: tests/test_full_configs_gpu.py
-                                            test_c5_rrdbnet_full[fp32x3]), else 'fp32' (exact-fp32 MFMA)."""
+                                            test_c5_rrdbnet_full[fp32x3]), else 'fp32' (exact-fp32 MFMA; USRNet
+                                            has an fp32x3 engine, tests/test_usrnet_x3_gpu.py, on explicit request
+                                            only)."""
     o = opt["netG"]
     if o.get("compute_dtype"):
         if o["compute_dtype"] not in ("bf16", "fp32", "fp32x3"):
@@ -84,7 +87,7 @@ def compute_dtype_of(opt):
     tr = opt.get("train") or {}
     if tr.get("amp_enabled"):
         return "bf16"
-    return "fp32x3" if o.get("net_type") in _X3_NETS else "fp32"
+    return "fp32x3" if o.get("net_type") in _X3_DEFAULT_NETS else "fp32"
 
 
 def _engine_kwargs(opt):
