@@ -35,7 +35,7 @@ typedef enum { KAIR_F32 = 0, KAIR_BF16 = 1, KAIR_F16 = 3 } kair_dtype;
  * operand in fp16's range) and every product as hi.hi + hi.lo + lo.hi with fp32 accumulation, rescaled by
  * 2^-(eA + eB): ~2^-21 relative per product, the precision class of fp32 arithmetic (one bf16 product:
  * 2^-8; bf16 pairs: 2^-16).  Operands: fp32 (split in the kernel) or fp16 hi planes with
- * kair_operand.lo_ptr (their stored values carry x3_exp).  Packed weights (kinds 9 / 17 / 18 / 19 / 20 / 21 with
+ * kair_operand.lo_ptr (their stored values carry x3_exp).  Packed weights (kinds 9 / 17 .. 23 with
  * an fp16 destination) hold w * 2^KAIR_X3_WEXP.  kair_gemm_nt's A and kair_gemm_tn's B may be the space-to-depth
  * operand (KAIR_LD_S2D) of an fp32 map with im_C % 8 == 0, K == 4 * im_C and whole im_H x im_W grids of rows (split
  * at the LDS commit; the 2x2 / stride-2 conv forward, the transposed conv's input gradient and both weight
@@ -200,7 +200,13 @@ typedef struct {
                           each row of the plain form as 64-column chunks alternating hi / lo, row length
                           2*ceil(rowlen/64)*64 (the layout the x3 NT kernels read, as kind 9);
                         20 the same pair form of kind 7: rows Np of 4*Kp columns, k = tap*Kp + kp (Kp % 8 == 0);
-                        21 the same pair form of kind 8: rows kp*4 + tap of Np columns (Np % 8 == 0) */
+                        21 the same pair form of kind 8: rows kp*4 + tap of Np columns (Np % 8 == 0);
+                        22 conv3x3 forward as x3 fp16 pairs of w 2^KAIR_X3_WEXP in kind 15's layout:
+                          [Np/16][9*Kp/32][2][64][8], k = tap*Kp + cip, the hi block of (nb, kb) followed by
+                          its lo block (lane l: row 16nb + l%16, k 32kb + 8(l/16) + j);
+                        23 conv3x3 dgrad form (kind 2 / 16 ordering) as the same fp16 pairs:
+                          [Kp/16][9*Np/32][2][64][8], rows = input channels, k = tap*Np + cop
+                          (22 / 23: kair_conv3x3_wr_x3's forward and input-gradient weights) */
   int N, K;          /* reference dims: linear (out,in); conv (Cout,Cin)                     */
   int nG, nGr, nGp;  /* out dim = nG groups of nGr real rows padded to nGp                   */
   int kG, kGr, kGp;  /* in  dim = kG groups of kGr real cols padded to kGp (kinds 1 / 9 only: kG*kGr
@@ -467,6 +473,19 @@ int kair_conv3x3_wr_ex(const void* x, int x_dtype, long ldx, int split, int flip
                        const float* bias, const float* resid, long ldr, void* out, int out_dtype, long ldo, void* out_lo,
                        int ps_r, int act, float slope, const void* gate, long ldg, void* acopy, long ldac, int acones,
                        int B, int H, int W, int C, int N, void* stream);
+
+/* kair_conv3x3_wr's split form in the fp16-pair arithmetic of KAIR_COMPUTE_X3 (the fp32x3 engine's 192 -> 192
+ * convs and their input gradients, instead of kair_gemm_nt over KAIR_LD_IM2COL3): x fp32 NHWC rows; the kernel
+ * forms hi = f16(x 2^ea), lo = f16(x 2^ea - hi) once per tile and multiplies hi.W_hi + hi.W_lo + lo.W_hi with
+ * w = pack kind 22 (forward) or 23 (input gradient: x = the output gradient, flip = 1, C = the packed output
+ * channels, N = the packed input channels), n_blocks = 12; out[m][n] = acc 2^-(ea + KAIR_X3_WEXP) + bias[n]
+ * (+ resid[m][n]), fp32 rows.  ea: the exponent of the image's class, a launch argument (activations: the
+ * engine's activation exponent; gradients: the step's gradient exponent).  C a multiple of 64, <= 192;
+ * 64 < N <= 192, N % 4 == 0; kair_conv3x3_wr_x3_tile: the tile (96 / 48 pixels), 0 = unsupported. */
+int kair_conv3x3_wr_x3_tile(int B, int H, int W, int C, int N);
+int kair_conv3x3_wr_x3(const float* x, long ldx, int ea, int flip, const void* w, int n_blocks, const float* bias,
+                       const float* resid, long ldr, float* out, long ldo, int B, int H, int W, int C, int N,
+                       void* stream);
 
 /* Narrow-output 3x3 convs (csrc/tail.hip): a 64-channel NHWC bf16 image <-> NR <= 4 output channels,
  * the last conv of the reconstruction head (network_swinir.py:745, :817 conv_last).

@@ -160,6 +160,9 @@ _SIGS = {
     "kair_conv3x3_wr_ex": [c_vp, c_int, c_long, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_int, c_long, c_vp,
                            c_int, c_int, c_float, c_vp, c_long, c_vp, c_long, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_vp],
+    "kair_conv3x3_wr_x3_tile": [c_int, c_int, c_int, c_int, c_int],
+    "kair_conv3x3_wr_x3": [c_vp, c_long, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_long, c_int, c_int, c_int,
+                           c_int, c_int, c_vp],
     "kair_conv3x3_narrow_dgrad_ws": [],
     "kair_conv3x3_narrow_dgrad": [c_vp, c_long, c_vp, c_int, c_vp, c_vp, c_int, c_long, c_int, c_int, c_int, c_int, c_vp],
     "kair_conv3x3_narrow_wgrad_ws": [c_int],
@@ -421,8 +424,8 @@ def epilogue(out, mode=OUT_ROWS, ldo=None, win=None, bias=None, act=ACT_NONE, sl
 def wmap(kind, N, K, n_groups=(1, None, None), k_groups=(1, None, None), n_perm=0):
     """n_groups = (G, real, padded) for the out dim; k_groups likewise for the in dim; n_perm = r*r
     stores the out dim sub-pixel-major (PixelShuffle SPM layouts).  Kinds: kair_wmap (kair_hip.h); the x3
-    fp16-pair forms are 9 / 17 / 18 / 19 (3x3 forward, linear, 3x3 dgrad, transposed linear) and 20 / 21 (the
-    2x2 forms 7 / 8)."""
+    fp16-pair forms are 9 / 17 / 18 / 19 (3x3 forward, linear, 3x3 dgrad, transposed linear), 20 / 21 (the
+    2x2 forms 7 / 8) and 22 / 23 (3x3 forward / dgrad in 16x16x32 fragment order: conv3x3_wr_x3)."""
     m = WMap()
     m.kind, m.N, m.K = kind, N, K
     m.n_perm = n_perm
@@ -687,6 +690,21 @@ def conv3x3_wr(x, ldx, flip, w, bias, resid, out, B, H, W, C, N, ldr=None, ldo=N
                                    act, slope, ptr(gate), ldg if ldg is not None else (gate.shape[-1] if gate is not None else 0),
                                    ptr(acopy), ldac if ldac is not None else (acopy.shape[-1] if acopy is not None else 0),
                                    acones, B, H, W, C, N, stream_ptr()), "conv3x3_wr")
+
+
+def conv3x3_wr_x3_tile(B, H, W, C, N):
+    """Tile (pixels) of kair_conv3x3_wr_x3 for this shape, 0 when unsupported."""
+    return lib().kair_conv3x3_wr_x3_tile(B, H, W, C, N)
+
+
+def conv3x3_wr_x3(x, ldx, x3_exp, flip, w, bias, resid, out, B, H, W, C, N, ldr=None, ldo=None):
+    """kair_conv3x3_wr_x3: the fp16-pair 3x3 conv with register-streamed weights on fp32 rows x (scaled by
+    2^x3_exp in the kernel); w = fp16 pack kind 22, or 23 with flip = 1 for an input gradient."""
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or w.dtype != torch.float16:
+        raise TypeError("conv3x3_wr_x3: fp32 rows in and out, fp16 packed weights")
+    check(lib().kair_conv3x3_wr_x3(ptr(x), ldx, int(x3_exp), int(flip), ptr(w), 12, ptr(bias), ptr(resid),
+                                   ldr if ldr is not None else (resid.shape[-1] if resid is not None else 0), ptr(out),
+                                   ldo if ldo is not None else out.shape[-1], B, H, W, C, N, stream_ptr()), "conv3x3_wr_x3")
 
 
 def conv3x3_narrow_dgrad_ws():

@@ -21,6 +21,13 @@
 // Epilogue per lane: 4 consecutive output channels of one pixel (bias, fp32 residual, fp32 / bf16
 // rows).  The tile's own pixels can be copied out as bf16 rows (a_copy, + a ones column) for the
 // weight gradient, as the halo kernel does.
+//
+// fp16-pair form (TH = _Float16, the fp32x3 engine's 192 -> 192 convs and their input gradients): the split
+// form's instruction stream on v_mfma_f32_16x16x32_f16.  The halo fill forms hi = f16(x 2^ea), lo = f16(x 2^ea - hi)
+// (ea a launch argument: the activation exponent forward, the step's gradient exponent backward), the weights
+// are fp16 pairs of w 2^KAIR_X3_WEXP (pack kinds 22 / 23), the accumulator is rescaled by 2^-(ea + ew) before
+// bias and residual.  The im2col GEMM on the x3 NT ring pulls the same fp32 image through the CU's LDS fill
+// path nine times and splits every activation 18 times; here it is loaded and split once per tile.
 #include "common.h"
 
 namespace {
@@ -46,6 +53,7 @@ struct ConvWrArgs {
   int act; float slope;              // KAIR_ACT_LEAKY: LeakyReLU(slope) before the store (no residual)
   const bf16* gate; long ldg;        // v *= (gate[m][n] > 0 ? 1 : slope): LeakyReLU' of a stored activation (rows)
   int psH, psW;                      // EM 2: the pre-shuffle grid (H / r, W / r) of the PixelUnshuffle store
+  float ascale, oscale;              // fp16-pair form: 2^ea on the image, 2^-(ea + ew) on the accumulator
   int B, H, W, C, N, flip;
   long tilesM;
   FDiv fc8, fhwd;                    // C / 8 and the halo row width (magic-number divisions)
@@ -62,14 +70,26 @@ template <bool SPLIT> struct WrGeom {
 // RN: 16-wide output fragments per wave (1: N <= 64, 3: N <= 192, 4: N <= 256).  EM 1: PixelShuffle
 // sub-pixel-major store (+ the lo plane of a bf16 pair output); EM 2: its inverse, PixelUnshuffle (an
 // upsampling conv's input gradient into the previous conv's pre-shuffle rows).
-template <typename TX, bool SPLIT, int BM, bool RESID, int RN, int EM>
+KAIR_DEV f32x4 wr_mfma(const bf16x8& w, const bf16x8& x, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
+}
+KAIR_DEV f32x4 wr_mfma(const f16x8& w, const f16x8& x, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0);
+}
+
+// TH: the 2-byte element of the halo and the weights -- bf16, or _Float16 (the fp16-pair form: fp32 image,
+// SPLIT, fp32 rows out, no a_copy)
+template <typename TX, bool SPLIT, int BM, bool RESID, int RN, int EM, typename TH = bf16>
 __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a) {
   constexpr bool PAIR = SPLIT && sizeof(TX) == 2;
+  constexpr bool X3 = sizeof(TH) == 2 && !__is_same(TH, bf16);
+  static_assert(!X3 || (SPLIT && sizeof(TX) == 4 && EM == 0), "fp16-pair form: fp32 image, split, row output");
+  typedef typename V8<TH>::t th8;
   constexpr int RM = BM / 16;
   constexpr int HALO = WrGeom<SPLIT>::HALO;
   constexpr int NB = SPLIT ? 2 : 1;                         // weight fragments per (rn, k-step)
-  __shared__ __attribute__((aligned(16))) bf16 sH[SPLIT ? 2 * HALO : HALO];
-  bf16* const sLo = sH + (SPLIT ? HALO : 0);
+  __shared__ __attribute__((aligned(16))) TH sH[SPLIT ? 2 * HALO : HALO];
+  TH* const sLo = sH + (SPLIT ? HALO : 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fq = lane >> 4;
   const int H = a.H, W = a.W, C = a.C;
@@ -91,9 +111,9 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
     hb[i] = ((ry + 1) * HWD + rx + 1) * PS + fq * 8;
   }
   // this wave's weight fragments: n blocks 3 w + rn, k-step s: one 1 KiB wave load per fragment
-  const bf16* wb = a.w + ((long)(RN * wave) * KS * NB) * 512 + lane * 8;
+  const TH* wb = (const TH*)a.w + ((long)(RN * wave) * KS * NB) * 512 + lane * 8;
   auto wfrag = [&](int rn, int s, int half) {
-    return *(const bf16x8*)(wb + (((long)rn * KS + s) * NB + half) * 512);
+    return *(const th8*)(wb + (((long)rn * KS + s) * NB + half) * 512);
   };
   float4 bias4[RN];
 #pragma unroll
@@ -103,14 +123,14 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
   }
 
   constexpr int PD = WrPD<RN, SPLIT>::PD, UNR = WrPD<RN, SPLIT>::UNR;   // UNR: lcm(PD, 2); KS = 18 C / 64 is a multiple
-  bf16x8 rb[PD][RN][NB];           // weight ring
+  th8 rb[PD][RN][NB];              // weight ring
   auto issue_w = [&](int slot, int s) {
 #pragma unroll
     for (int rn = 0; rn < RN; ++rn)
 #pragma unroll
       for (int h = 0; h < NB; ++h) rb[slot][rn][h] = wfrag(rn, s, h);
   };
-  bf16x8 ra[2][RM][NB];            // activation fragments, one k-step ahead
+  th8 ra[2][RM][NB];               // activation fragments, one k-step ahead
   auto read_a = [&](int buf, int s) {
     const int tap = s / cpsP, c0 = (s - tap * cpsP) * 32;
     int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
@@ -118,8 +138,8 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
     const int off = (dy * HWD + dx) * PS + c0;
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
-      ra[buf][i][0] = *(const bf16x8*)(sH + hb[i] + off);
-      if constexpr (SPLIT) ra[buf][i][1] = *(const bf16x8*)(sLo + hb[i] + off);
+      ra[buf][i][0] = *(const th8*)(sH + hb[i] + off);
+      if constexpr (SPLIT) ra[buf][i][1] = *(const th8*)(sLo + hb[i] + off);
     }
   };
 
@@ -185,11 +205,17 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
           if constexpr (sizeof(TX) == 4) {
             const float4 u = __builtin_bit_cast(float4, v0[i]), v = __builtin_bit_cast(float4, v1[i]);
             const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-            bf16x8 hh, ll;
+            th8 hh, ll;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              hh[e] = (bf16)f[e];
-              if constexpr (SPLIT) ll[e] = (bf16)(f[e] - (float)hh[e]);
+              if constexpr (X3) {   // the pair of x 2^ea (common.h opaque: no conversion fused with the scaling)
+                const float w = opaque(f[e] * a.ascale);
+                hh[e] = (TH)w;
+                ll[e] = (TH)(w - (float)hh[e]);
+              } else {
+                hh[e] = (TH)f[e];
+                if constexpr (SPLIT) ll[e] = (TH)(f[e] - (float)hh[e]);
+              }
             }
             qh = __builtin_bit_cast(uint4, hh);
             if constexpr (SPLIT) ql = __builtin_bit_cast(uint4, ll);
@@ -200,7 +226,7 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
           if (!okv[i]) qh = ql = make_uint4(0, 0, 0, 0);
           *(uint4*)(sH + pix * PS + c8 * 8) = qh;
           if constexpr (SPLIT) *(uint4*)(sLo + pix * PS + c8 * 8) = ql;
-          if (a.acopy) {   // the tile's own pixels: bf16 copy (+ ones column) for the weight gradient
+          if (!X3 && a.acopy) {   // the tile's own pixels: bf16 copy (+ ones column) for the weight gradient
             const int hr = fdiv(pix, a.fhwd), hc = pix - hr * HWD;
             if (hr >= 1 && hr <= RPT && hc >= 1 && hc <= XW) {
               uint4 qc = qh;
@@ -231,10 +257,10 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
       for (int i = 0; i < RM; ++i)
 #pragma unroll
         for (int rn = 0; rn < RN; ++rn) {
-          acc[i][rn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[ws][rn][0], ra[ab][i][0], acc[i][rn], 0, 0, 0);
+          acc[i][rn] = wr_mfma(rb[ws][rn][0], ra[ab][i][0], acc[i][rn]);
           if constexpr (SPLIT) {
-            acc[i][rn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[ws][rn][1], ra[ab][i][0], acc[i][rn], 0, 0, 0);
-            acc[i][rn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[ws][rn][0], ra[ab][i][1], acc[i][rn], 0, 0, 0);
+            acc[i][rn] = wr_mfma(rb[ws][rn][1], ra[ab][i][0], acc[i][rn]);
+            acc[i][rn] = wr_mfma(rb[ws][rn][0], ra[ab][i][1], acc[i][rn]);
           }
         }
       issue_w(ws, wstep(s + PD < KSP ? s + PD : KSP - 1));
@@ -255,6 +281,7 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
         const int n = 16 * RN * wave + 16 * rn + 4 * fq;
         if (n >= a.N) continue;
         const float4 bb = bias4[rn];
+        if constexpr (X3) acc[i][rn] *= a.oscale;
         float v[4] = {acc[i][rn][0] + bb.x, acc[i][rn][1] + bb.y, acc[i][rn][2] + bb.z, acc[i][rn][3] + bb.w};
         if constexpr (RESID) {
           v[0] += ex[i][rn].x; v[1] += ex[i][rn].y; v[2] += ex[i][rn].z; v[3] += ex[i][rn].w;
@@ -280,7 +307,7 @@ __global__ __launch_bounds__(WR_NT, 1) void conv3x3_wr_kernel(const ConvWrArgs a
           const int yl = yy / r, xl = xx / r;
           o = (((long)bi * a.psH + yl) * a.psW + xl) * a.ldo + ((yy - yl * r) * r + (xx - xl * r)) * a.N + n;
         }
-        if (a.odt == KAIR_BF16) {
+        if (!X3 && a.odt == KAIR_BF16) {
           const bf16x4 hv = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
           *(bf16x4*)((bf16*)a.out + o) = hv;
           if (a.out_lo)
@@ -393,6 +420,7 @@ extern "C" int kair_conv3x3_wr_ex(const void* x, int x_dtype, long ldx, int spli
   a.out_lo = (bf16*)out_lo; a.ps_r = pr;
   a.gate = (const bf16*)gate; a.ldg = ldg;
   a.psH = pr ? H / pr : 0; a.psW = pr ? W / pr : 0;
+  a.ascale = a.oscale = 1.f;
   KAIR_CHECK_ARG(act == KAIR_ACT_NONE || (act == KAIR_ACT_LEAKY && !resid && !gate),
                  "conv3x3_wr: act none, or LeakyReLU without residual / gate");
   a.act = act; a.slope = slope;
@@ -443,4 +471,50 @@ extern "C" int kair_conv3x3_wr(const void* x, int x_dtype, long ldx, int split, 
                                long ldac, int acones, int B, int H, int W, int C, int N, void* stream) {
   return kair_conv3x3_wr_ex(x, x_dtype, ldx, split, flip, w, n_blocks, bias, resid, ldr, out, out_dtype, ldo, nullptr, 0,
                             KAIR_ACT_NONE, 0.f, nullptr, 0, acopy, ldac, acones, B, H, W, C, N, stream);
+}
+
+/* The fp16-pair ("fp32x3") form: see kair_hip.h. */
+extern "C" int kair_conv3x3_wr_x3_tile(int B, int H, int W, int C, int N) {
+  if (N <= 64 || N > 192) return 0;   // the 48-channels-per-wave form only
+  return kair_conv3x3_wr_tile(1, B, H, W, C, N);
+}
+
+extern "C" int kair_conv3x3_wr_x3(const float* x, long ldx, int ea, int flip, const void* w, int n_blocks,
+                                  const float* bias, const float* resid, long ldr, float* out, long ldo, int B, int H,
+                                  int W, int C, int N, void* stream) {
+  KAIR_CHECK_ARG(x && w && out && B > 0, "conv3x3_wr_x3: null operand");
+  KAIR_CHECK_ARG(ea > -100 && ea < 100, "conv3x3_wr_x3: image exponent out of range");
+  const int BM = kair_conv3x3_wr_x3_tile(B, H, W, C, N);
+  KAIR_CHECK_ARG(BM == 48 || BM == 96, "conv3x3_wr_x3: unsupported geometry (B %d, H %d, W %d, C %d, N %d)", B, H, W, C, N);
+  KAIR_CHECK_ARG(n_blocks == 12, "conv3x3_wr_x3: the packed weight needs 192 output rows (12 blocks of 16), got %d blocks",
+                 n_blocks);
+  KAIR_CHECK_ARG(ldx >= C && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0,
+                 "conv3x3_wr_x3: image rows 16-byte aligned, ldx >= C");
+  KAIR_CHECK_ARG(ldo >= N && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0, "conv3x3_wr_x3: output rows");
+  KAIR_CHECK_ARG(!resid || (ldr >= N && ldr % 4 == 0 && ((uintptr_t)resid & 15) == 0), "conv3x3_wr_x3: residual rows");
+  KAIR_CHECK_ARG(!bias || ((uintptr_t)bias & 15) == 0, "conv3x3_wr_x3: bias alignment");
+  const long M = (long)B * H * W;
+  KAIR_CHECK_ARG(M * (ldx > ldo ? ldx : ldo) < (1L << 31), "conv3x3_wr_x3: operands past 2^31 elements");
+  ConvWrArgs a;
+  a.x = x; a.ldx = ldx; a.w = (const bf16*)w; a.bias = bias; a.resid = resid; a.ldr = ldr;
+  a.out = out; a.odt = KAIR_F32; a.ldo = ldo; a.acopy = nullptr; a.ldac = 0; a.acones = -1;
+  a.out_lo = nullptr; a.ps_r = 0; a.act = KAIR_ACT_NONE; a.slope = 0.f; a.gate = nullptr; a.ldg = 0;
+  a.psH = a.psW = 0;
+  a.ascale = ldexpf(1.f, ea); a.oscale = ldexpf(1.f, -(ea + KAIR_X3_WEXP));
+  a.B = B; a.H = H; a.W = W; a.C = C; a.N = N; a.flip = flip;
+  a.tilesM = M / BM;
+  a.fc8 = make_fdiv(C / 8);
+  a.fhwd = make_fdiv((W < BM ? W : BM) + 2);
+  const int ncu = wr_num_cus();
+  const int grid = (int)(a.tilesM < ncu ? a.tilesM : ncu);
+  hipStream_t s = (hipStream_t)stream;
+#define KAIR_WRX(BMV, RV) KAIR_LAUNCH((conv3x3_wr_kernel<float, true, BMV, RV, 3, 0, f16>), dim3(grid), dim3(WR_NT), 0, s, a)
+  if (BM == 48) {
+    if (resid) KAIR_WRX(48, true); else KAIR_WRX(48, false);
+  } else {
+    if (resid) KAIR_WRX(96, true); else KAIR_WRX(96, false);
+  }
+#undef KAIR_WRX
+  KAIR_CHECK_LAUNCH();
+  return 0;
 }

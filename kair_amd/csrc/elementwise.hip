@@ -247,9 +247,14 @@ KAIR_DEV void pack_chunk(const float* __restrict__ src, bf16* __restrict__ dst, 
 // Np of 9 Kp (tap-major), 17 rows Np of Kp, 18 rows Kp of 9 Np (tap-major), 19 rows Kp of Np; the 2x2 forms: 20 (the
 // pair of kind 7) rows Np of 4 Kp (tap-major), 21 (the pair of kind 8) rows kp * 4 + tap of Np; a chunk never straddles
 // a tap (Kp / Np % 8 == 0, pack_pair_vec).
+// Kinds 22 / 23 (fp16 only: kair_conv3x3_wr_x3's weights) hold the same values as 9 / 18 in 16x16x32 fragment order
+// with hi/lo halves, [rows / 16][rowlen / 32][2][64 lanes][8] (kind 15's layout): work item u is lane u % 64 of
+// fragment u / 64 -- row 16 rb + lane % 16, columns 32 kb + 8 (lane / 16) .. + 8.
 __host__ __device__ inline bool pack_pair_vec(const kair_wmap& mp, int dt) {
   if (dt != KAIR_F16 && dt != KAIR_BF16) return false;
   const int Np = mp.nG * mp.nGp, Kp = mp.kG * mp.kGp;
+  if (mp.kind == 22) return dt == KAIR_F16 && Np % 16 == 0 && Kp % 8 == 0 && (9 * Kp) % 32 == 0;
+  if (mp.kind == 23) return dt == KAIR_F16 && Kp % 16 == 0 && Np % 8 == 0 && (9 * Np) % 32 == 0;
   if (mp.kind == 9 || mp.kind == 17 || mp.kind == 20) return Kp % 8 == 0;
   if (mp.kind == 18 || mp.kind == 19 || mp.kind == 21) return Np % 8 == 0;
   return false;
@@ -257,17 +262,25 @@ __host__ __device__ inline bool pack_pair_vec(const kair_wmap& mp, int dt) {
 
 KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ dst, int dt, const kair_wmap& mp, int u) {
   const int Np = mp.nG * mp.nGp, Kp = mp.kG * mp.kGp;
-  const bool rows_n = mp.kind == 9 || mp.kind == 17 || mp.kind == 20;   // rows are output channels (else input channels)
-  const int rowlen = mp.kind == 9 ? 9 * Kp : mp.kind == 17 ? Kp : mp.kind == 18 ? 9 * Np : mp.kind == 20 ? 4 * Kp : Np;
+  const bool frag = mp.kind == 22 || mp.kind == 23;   // fragment order (values of kinds 9 / 18)
+  const bool rows_n = mp.kind == 9 || mp.kind == 17 || mp.kind == 20 || mp.kind == 22;   // rows are output channels (else input channels)
+  const int rowlen = (mp.kind == 9 || mp.kind == 22) ? 9 * Kp : mp.kind == 17 ? Kp : (mp.kind == 18 || mp.kind == 23) ? 9 * Np
+                     : mp.kind == 20 ? 4 * Kp : Np;
   const int rl64 = (rowlen + 63) / 64 * 64, cpr = rl64 / 8;
-  const int row = u / cpr, k0 = (u - row * cpr) * 8;
+  int row = u / cpr, k0 = (u - row * cpr) * 8;
+  if (frag) {
+    const int ln = u & 63, blk = u >> 6, KB = rowlen / 32;
+    row = (blk / KB) * 16 + (ln & 15);
+    k0 = (blk - (blk / KB) * KB) * 32 + 8 * (ln >> 4);
+  }
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = 0.f;
   if (k0 < rowlen) {
     const int rr = rows_n ? nperm_fwd(mp, unpad(row, mp.nG, mp.nGr, mp.nGp))
                           : unpad(mp.kind == 21 ? row >> 2 : row, mp.kG, mp.kGr, mp.kGp);
-    const int seg = (mp.kind == 9 || mp.kind == 20) ? Kp : (mp.kind == 18) ? Np : rowlen;   // tap-major forms: one tap per segment
+    const int seg = (mp.kind == 9 || mp.kind == 20 || mp.kind == 22) ? Kp : (mp.kind == 18 || mp.kind == 23) ? Np
+                    : rowlen;   // tap-major forms: one tap per segment
     const int tap = mp.kind == 21 ? (row & 3) : k0 / seg, c0 = mp.kind == 21 ? k0 : k0 - (k0 / seg) * seg;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -276,13 +289,14 @@ KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ 
       if (rows_n) { n = rr; k = unpad(c, mp.kG, mp.kGr, mp.kGp); }
       else { n = nperm_fwd(mp, unpad(c, mp.nG, mp.nGr, mp.nGp)); k = rr; }
       if (n < 0 || k < 0) continue;
-      if (mp.kind == 9) v[j] = src[((long)n * mp.K + k % mp.K) * 9 + tap];   // % K: tied in-dim copies
-      else if (mp.kind == 18) v[j] = src[((long)n * mp.K + k) * 9 + tap];
+      if (mp.kind == 9 || mp.kind == 22) v[j] = src[((long)n * mp.K + k % mp.K) * 9 + tap];   // % K: tied in-dim copies
+      else if (mp.kind == 18 || mp.kind == 23) v[j] = src[((long)n * mp.K + k) * 9 + tap];
       else if (mp.kind == 20 || mp.kind == 21) v[j] = src[((long)n * mp.K + k) * 4 + tap];
       else v[j] = src[(long)n * mp.K + k];
     }
   }
-  const long o = (long)row * 2 * rl64 + ((k0 >> 6) << 7) + (k0 & 63);
+  const long o = frag ? (long)(u >> 6) * 1024 + (u & 63) * 8 : (long)row * 2 * rl64 + ((k0 >> 6) << 7) + (k0 & 63);
+  const int lo_off = frag ? 512 : 64;
   if (dt == KAIR_F16) {
     f16x8 hi, lo;
 #pragma unroll
@@ -292,7 +306,7 @@ KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ 
       lo[j] = (f16)(w - (float)hi[j]);
     }
     *(f16x8*)((f16*)dst + o) = hi;
-    *(f16x8*)((f16*)dst + o + 64) = lo;
+    *(f16x8*)((f16*)dst + o + lo_off) = lo;
   } else {
     bf16x8 hi, lo;
 #pragma unroll
@@ -301,7 +315,7 @@ KAIR_DEV void pack_pair_chunk(const float* __restrict__ src, void* __restrict__ 
       lo[j] = (bf16)(v[j] - (float)hi[j]);
     }
     *(bf16x8*)((bf16*)dst + o) = hi;
-    *(bf16x8*)((bf16*)dst + o + 64) = lo;
+    *(bf16x8*)((bf16*)dst + o + lo_off) = lo;
   }
 }
 
@@ -861,16 +875,16 @@ static int pack_total(const kair_wmap& mp, int dst_dtype, long* total) {
                  "pack_weight: the hi/lo split forms 12 / 15 are bf16 only");
   KAIR_CHECK_ARG(mp.kind != 9 || dst_dtype == KAIR_BF16 || dst_dtype == KAIR_F16,
                  "pack_weight: kind 9 is a bf16 or (x3) fp16 pair form");
-  KAIR_CHECK_ARG(dst_dtype == KAIR_F32 || dst_dtype == KAIR_BF16 || ((mp.kind == 9 || (mp.kind >= 17 && mp.kind <= 21)) &&
+  KAIR_CHECK_ARG(dst_dtype == KAIR_F32 || dst_dtype == KAIR_BF16 || ((mp.kind == 9 || (mp.kind >= 17 && mp.kind <= 23)) &&
                                                                      dst_dtype == KAIR_F16),
-                 "pack_weight: fp16 destinations are the x3 pair forms (kinds 9, 17, 18, 19, 20, 21)");
+                 "pack_weight: fp16 destinations are the x3 pair forms (kinds 9, 17 .. 23)");
   KAIR_CHECK_ARG(mp.nG > 0 && mp.nGr > 0 && mp.nGp >= mp.nGr && mp.nG * mp.nGr == mp.N, "pack_weight: bad N map");
   // kinds 1 / 9 (conv forward) may repeat the in dim (kG * kGr a multiple of K: tied copies, e.g. the
   // hi / lo halves of a split input image); every other kind maps it one to one
   KAIR_CHECK_ARG(mp.kind == 4 ||
                      (mp.kG > 0 && mp.kGr > 0 && mp.kGp >= mp.kGr &&
                       (mp.kG * mp.kGr == mp.K ||
-                       ((mp.kind == 1 || mp.kind == 9 || mp.kind == 15) && mp.K > 0 && (mp.kG * mp.kGr) % mp.K == 0))),
+                       ((mp.kind == 1 || mp.kind == 9 || mp.kind == 15 || mp.kind == 22) && mp.K > 0 && (mp.kG * mp.kGr) % mp.K == 0))),
                  "pack_weight: bad K map");
   KAIR_CHECK_ARG(mp.n_perm <= 1 || (mp.nG == 1 && mp.N % mp.n_perm == 0), "pack_weight: n_perm needs nG == 1, N %% n_perm == 0");
   const long Np = (long)mp.nG * mp.nGp, Kp = (long)mp.kG * mp.kGp;
@@ -896,6 +910,14 @@ static int pack_total(const kair_wmap& mp, int dst_dtype, long* total) {
     *total = rows * 2 * ((rowlen + 63) / 64) * 64;
     return 0;
   }
+  if (mp.kind == 22 || mp.kind == 23) {   // fp16 pairs in 16x16x32 fragment order: the chunked packer only
+    KAIR_CHECK_ARG(dst_dtype == KAIR_F16, "pack_weight: kinds 22 / 23 are fp16 pairs");
+    KAIR_CHECK_ARG(pack_pair_vec(mp, dst_dtype), "pack_weight: kind 22 needs Np %% 16 == 0, Kp %% 8 == 0, 9 Kp %% 32 == 0; "
+                                                 "kind 23 Kp %% 16 == 0, Np %% 8 == 0, 9 Np %% 32 == 0");
+    KAIR_CHECK_ARG(2 * Np * 9 * Kp / 16 < (1L << 31), "pack_weight: kind %d pack too large", mp.kind);
+    *total = 2 * Np * 9 * Kp;
+    return 0;
+  }
   if (mp.kind == 0 || mp.kind == 3 || mp.kind == 10 || mp.kind == 13 || mp.kind == 14) *total = Np * Kp;
   else if (mp.kind == 12) *total = 2 * Np * Kp;
   else if (mp.kind == 1 || mp.kind == 2 || mp.kind == 16) *total = Np * 9 * Kp;
@@ -911,7 +933,7 @@ extern "C" int kair_pack_weight(const float* src, void* dst, int dst_dtype, cons
   KAIR_CHECK_ARG(src && dst && map, "pack_weight: null pointer");
   long total;
   if (int rc = pack_total(*map, dst_dtype, &total)) return rc;
-  if (map->kind == 20 || map->kind == 21) {
+  if (map->kind >= 20 && map->kind <= 23) {
     KAIR_LAUNCH(pack_pair_kernel, dim3(nblk(total / 16, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, dst_dtype,
                        *map, total / 16);
     KAIR_CHECK_LAUNCH();

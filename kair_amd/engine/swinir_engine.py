@@ -146,7 +146,8 @@ class _Conv:
         2 x Cip channels read through tied weights: the SwinIR tail under split_act).
         narrow: a 64 -> NR <= 4 conv run by the narrow-output kernels (kair_conv3x3_narrow_*): its forward
         form is pack kind 15 (16x16x32 fragment order, hi/lo halves), the backward reads the fp32 weight.
-        wr: a 192 -> 192 conv also packed for kair_conv3x3_wr: forward pack kind 15, input gradient kind 16."""
+        wr: a 192 -> 192 conv also packed for kair_conv3x3_wr: forward pack kind 15, input gradient kind 16
+        (fp32x3: kair_conv3x3_wr_x3's fp16 pairs, kinds 22 / 23)."""
         self.w, self.b = mod.weight, mod.bias
         Co, Ci = self.w.shape[:2]
         self.Co, self.Ci, self.Cop, self.Cip = Co, Ci, Cop, Cip
@@ -186,13 +187,19 @@ class _Conv:
             self.mapp16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
             self.Wp16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
         # wr_n64: conv_before_upsample (192 -> 64) on kair_conv3x3_wr's N <= 64 form
-        self.wr_n64 = bool(wr) and not self.wr and not self.wr_pair and Cop == 64 and Cip == 192 and self.split and not tied_in
+        self.wr_n64 = (bool(wr) and not self.wr and not self.wr_pair and Cop == 64 and Cip == 192 and self.split and
+                       not tied_in and not self.x3)
         if self.wr_n64:
             self.mapc = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
             self.Wc15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
             self.mapc16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
             self.Wc16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
-        if self.wr:
+        if self.wr and self.x3:   # fp16 pairs of w 2^KAIR_X3_WEXP in fragment order (same element counts)
+            self.map15 = H.wmap(22, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.float16)
+            self.map16 = H.wmap(23, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wd16 = torch.empty(Cip * 2 * 9 * Cop, device=dev, dtype=torch.float16)
+        elif self.wr:
             self.map15 = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
             self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
             self.map16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
@@ -366,7 +373,8 @@ class SwinIREngine:
         # the '1conv' RSTB / conv_after_body convs (192 -> 192) and their input gradients on the
         # register-streamed-weight kernel (kair_conv3x3_wr, csrc/conv_wr.hip) where the per-GPU batch gives
         # it enough tiles (plan: P["conv_wr"]); the LDS-ring halo kernel otherwise
-        self.conv_wr = bool(conv_wr) and self.split_act and self.Cp == 192 and self.C % 4 == 0
+        # (fp32x3: the same convs on its fp16-pair form, kair_conv3x3_wr_x3, instead of the im2col GEMM on the NT ring)
+        self.conv_wr = bool(conv_wr) and (self.split_act or self.x3) and self.Cp == 192 and self.C % 4 == 0
         self.device = net.conv_first.weight.device
         dev = self.device
         self.mean = net.mean.view(-1).to(dev, torch.float32).contiguous()
@@ -669,6 +677,9 @@ class SwinIREngine:
                 if not isinstance(r, _Resi3):
                     P["conv_bf"][id(r)] = (torch.zeros(M, Cp, device=dev, dtype=T), torch.zeros(M, Cp, device=dev, dtype=T))
                     P["conv_bf"][id(r)][1][:, self.C] = 1.0
+        if self.x3:   # kair_conv3x3_wr_x3 under the same rule (the x3 NT ring otherwise)
+            P["conv_wr"] = bool(self.conv_wr and H.conv3x3_wr_x3_tile(B, Hh, Ww, Cp, Cp) > 0 and
+                                M // 96 >= self.conv_wr_min_tiles)
         # one shared wgrad workspace sized for the largest (splits * N * K)
         P["wg_ws"] = e(self._max_wgrad_ws(M, P))
         P["wg_ws2"] = (e(P["wg_ws"].numel() * max(1, -self.side_ctas)) if self.grouped_wgrad or self.side_stream
@@ -763,6 +774,9 @@ class SwinIREngine:
         if not isinstance(r, _Resi3):
             # training: the halo conv also leaves the bf16 weight-gradient operand (1.0 in channel C)
             ac = (P["conv_bf"][id(r)][1], self.C) if P.get("conv_halo") else None
+            if self.x3 and P.get("conv_wr") and r.wr:
+                H.conv3x3_wr_x3(src, Cp, self._ax, 0, r.Wf15, r.bp, resid, out, P["B"], Hh, Ww, Cp, Cp)
+                return
             if P.get("conv_wr") and r.wr:
                 assert src.dtype == torch.float32 and resid.dtype == torch.float32
                 H.conv3x3_wr(src, Cp, 0, r.Wf15, r.bp, resid, out, P["B"], Hh, Ww, Cp, Cp, acopy=ac[0], acones=ac[1],
@@ -785,7 +799,9 @@ class SwinIREngine:
         g = lambda p: grads[p]
         if not isinstance(r, _Resi3):
             ac = (P["conv_bf"][id(r)][0], -1) if P.get("conv_halo") else None
-            if P.get("conv_wr") and r.wr:
+            if self.x3 and P.get("conv_wr") and r.wr:   # (the weight gradient reads the fp32 rows: no copies)
+                H.conv3x3_wr_x3(G, Cp, self._ax, 1, r.Wd16, None, None, D, P["B"], Hh, Ww, Cp, Cp)
+            elif P.get("conv_wr") and r.wr:
                 H.conv3x3_wr(G, Cp, 1, r.Wd16, None, None, D, P["B"], Hh, Ww, Cp, Cp, acopy=ac[0], split=False)
             else:
                 self._nt(H.im2col(G, Hh, Ww, Cp, flip=True), H.rows(r.Wd), H.epilogue(D, acopy=ac), M, Cp, 9 * Cp, cd)
