@@ -1,0 +1,283 @@
+"""kair_swin_attn_fwd and kair_swin_mlp_bwd (csrc/swin_fused.hip) against float64 torch restatements of the
+two Swin block halves on hand-built tensors:
+
+    mid = x + s * proj(W-MSA(LN1(x)))              network_swinir.py:239-272, WindowAttention.forward :114-145
+    d(mid) = D + LN2-backward(fc1^T(fc2^T(s D) * GELU'))        the backward of :274-276, Mlp.forward :24-30
+
+Every stage is checked from the kernel's own stored result of the stage before it (products in float64 on the
+bf16 operands), so an assertion sees one rounding step.  The shapes are the smallest window grid with all nine
+shift-mask regions (2 x 3 windows, non-square), row strides that are not the packed width, a DropPath scale per
+sample, and for the backward one size at which a workgroup takes a second tile."""
+import pytest
+import torch
+
+from kair_amd import _hip as H
+from oracle.swinir import relative_position_index, shift_region_mask
+
+pytestmark = pytest.mark.gpu
+dev = torch.device("cuda", 0)
+NH, CP, HD, HDP = 6, 192, 360, 384
+SENT = 7.0
+
+
+def rel_err(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+
+
+def max_err(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+def win_perm(B, Hh, Ww, ws, shift):
+    """row m (window order) -> token index: roll(-shift) + window_partition, network_swinir.py:250-256"""
+    idx = torch.arange(B * Hh * Ww).view(B, Hh, Ww)
+    idx = torch.roll(idx, (-shift, -shift), (1, 2))
+    return idx.view(B, Hh // ws, ws, Ww // ws, ws).permute(0, 1, 3, 2, 4).reshape(-1)
+
+
+def _pack(w, kind, n_grp, k_grp):
+    Np, Kp = n_grp[0] * n_grp[2], k_grp[0] * k_grp[2]
+    shape = {10: (Np, Kp), 12: (2 * Np, Kp), 13: (Kp, Np)}[kind]
+    out = torch.empty(shape, device=dev, dtype=torch.bfloat16)
+    H.pack_weight(w.to(dev), out, H.wmap(kind, w.shape[0], w.shape[1], n_grp, k_grp))
+    return out
+
+
+def _w64(w, split):
+    """the weight the kernel multiplies by: bf16(w), or the hi + lo bf16 pair of pack kind 12"""
+    hi = w.to(torch.bfloat16)
+    if not split:
+        return hi.double()
+    return hi.double() + (w - hi.float()).to(torch.bfloat16).double()
+
+
+class _AttnCase:
+    """Inputs and output buffers of one kair_swin_attn_fwd call (B 2, 16 x 24 tokens, 12 windows)."""
+    B, Hh, Ww = 2, 16, 24
+    LDX = LDOUT = 200
+    LDLN = 208
+
+    def __init__(self, C, hd, w_split, with_scale=True):
+        B, Hh, Ww = self.B, self.Hh, self.Ww
+        self.C, self.hd, self.w_split = C, hd, w_split
+        self.M = M = B * Hh * Ww
+        self.nWin = nWin = M // 64
+        g = torch.Generator().manual_seed(11 + C)
+        self.x = torch.zeros(M, self.LDX)
+        self.x[:, :C] = torch.randn(M, C, generator=g) * 1.5 + 0.3
+        self.gamma, self.beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+        self.wqkv, self.bqkv = 0.05 * torch.randn(3 * C, C, generator=g), 0.05 * torch.randn(3 * C, generator=g)
+        self.wproj, self.bproj = 0.05 * torch.randn(C, C, generator=g), 0.05 * torch.randn(C, generator=g)
+        self.table = torch.randn(225, NH, generator=g) * 0.5
+        self.rowscale = torch.tensor([0.0, 1 / 0.7]) if with_scale else None
+        kind = 12 if w_split else 10   # as swinir_engine._Lin(frag=True, split=...) packs blk.qkv / blk.proj
+        self.Wqkv = _pack(self.wqkv, kind, (3 * NH, hd, 32), (1, C, CP))
+        self.Wproj = _pack(self.wproj, kind, (1, C, CP), (NH, hd, 32))
+        bq = torch.zeros(3 * NH, 32)
+        bq[:, :hd] = self.bqkv.view(3 * NH, hd)
+        bp = torch.zeros(CP)
+        bp[:C] = self.bproj
+        self.bq_d, self.bp_d = bq.view(-1).to(dev), bp.to(dev)
+        self.x_d, self.gamma_d, self.beta_d, self.table_d = (t.to(dev) for t in (self.x, self.gamma, self.beta, self.table))
+        self.rs_d = self.rowscale.to(dev) if with_scale else None
+        self.ln = torch.full((M, self.LDLN), SENT, device=dev, dtype=torch.bfloat16)
+        self.mean, self.rstd = torch.full((M,), SENT, device=dev), torch.full((M,), SENT, device=dev)
+        self.qkv = torch.full((3, nWin, NH, 64, 32), SENT, device=dev, dtype=torch.bfloat16)
+        self.O = torch.full((M, NH * 32), SENT, device=dev, dtype=torch.bfloat16)
+        self.lse = torch.full((nWin, NH, 64), SENT, device=dev)
+        self.out = torch.full((M, self.LDOUT), SENT, device=dev)
+
+    def run(self, shift, nh=NH, Hh=None, ldx=None, rows_per_scale=None):
+        Hh = self.Hh if Hh is None else Hh
+        H.swin_attn_fwd(self.x_d, self.LDX if ldx is None else ldx, self.gamma_d, self.beta_d, 1e-5, self.C, self.ln, self.LDLN,
+                        self.mean, self.rstd, self.Wqkv, self.bq_d, self.qkv, self.table_d, self.hd ** -0.5, self.O, NH * 32,
+                        self.hd, self.lse, self.Wproj, self.bp_d, self.rs_d,
+                        self.Hh * self.Ww if rows_per_scale is None else rows_per_scale, self.out, self.LDOUT, self.nWin, nh,
+                        Hh, self.Ww, shift, w_split=self.w_split)
+
+
+def _check_attn(case, shift):
+    C, hd, M, nWin, B, Hh, Ww = case.C, case.hd, case.M, case.nWin, case.B, case.Hh, case.Ww
+    case.run(shift)
+    torch.cuda.synchronize()
+    perm = win_perm(B, Hh, Ww, 8, shift)
+
+    # LN1 statistics (token order): the bounds of test_mlp_fused_gpu.py::test_swin_mlp_fwd_vs_float64
+    x64 = case.x[:, :C].double()
+    mu = x64.mean(1)
+    rs = 1.0 / torch.sqrt(x64.var(1, unbiased=False) + 1e-5)
+    assert (case.mean.cpu().double() - mu).abs().max().item() < 1e-5
+    assert ((case.rstd.cpu().double() - rs).abs() / rs).max().item() < 1e-5
+    # LN1 rows, window order; bf16 rounding bound of the same test
+    lnr = ((x64 - mu[:, None]) * rs[:, None] * case.gamma.double() + case.beta.double())[perm]
+    lng = case.ln.cpu().double()
+    assert (lng[:, :C] - lnr).abs().max().item() < 2e-2 * lnr.abs().max().item()
+    assert (lng[:, C] == 1).all() and (lng[:, C + 1:CP] == 0).all()
+    assert (lng[:, CP:] == SENT).all()                                   # past the packed width: not the kernel's
+
+    # q / k / v from the stored LN rows: TOL[BF16][0] of test_kernels_gpu.py (2e-2, norm-relative)
+    ref = lng[:, :C] @ _w64(case.wqkv, case.w_split).t() + case.bqkv.double()        # [M, 3 C], window-order rows
+    ref = ref.view(nWin, 64, 3, NH, hd).permute(2, 0, 3, 1, 4)                       # [3][nWin][nh][64][hd]
+    got = case.qkv.cpu().double()
+    for p in range(3):
+        assert rel_err(got[p, ..., :hd], ref[p]) < 2e-2, p
+    assert (got[..., hd:] == 0).all()
+
+    # attention from the stored q / k / v (q is stored unscaled: the kernel applies scale to S), bias and mask
+    # built as network_swinir.py builds them; the bf16 bound of test_kernels_gpu.py::test_window_attention_fwd_bwd
+    q, k, v = (got[p, ..., :hd] for p in range(3))
+    bias = case.table.double()[relative_position_index(8).view(-1)].view(64, 64, NH).permute(2, 0, 1)
+    s = (q * hd ** -0.5) @ k.transpose(-2, -1) + bias
+    if shift:
+        mask = shift_region_mask(Hh, Ww, 8, shift).double()
+        s = (s.view(B, -1, NH, 64, 64) + mask[None, :, None]).view(-1, NH, 64, 64)
+    o_ref = (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3)                           # [nWin][64][nh][hd]
+    Og = case.O.cpu().double().view(nWin, 64, NH, 32)
+    assert rel_err(Og[..., :hd], o_ref) < 1.5e-2
+    assert rel_err(case.lse, torch.logsumexp(s, -1)) < 1.5e-2
+    pad = Og[..., hd:].clone()
+    assert (pad[:, :, 0, 0] == 1).all()                                              # O[:, o_ones_col]
+    pad[:, :, 0, 0] = 0
+    assert (pad == 0).all()
+
+    # proj + DropPath + residual from the stored O, scattered to token order: the err < 1e-4 form of
+    # test_swin_mlp_fwd_vs_float64
+    y = Og[..., :hd].reshape(M, C) @ _w64(case.wproj, case.w_split).t() + case.bproj.double()
+    sc = case.rowscale.double().repeat_interleave(Hh * Ww) if case.rowscale is not None else torch.ones(M, dtype=torch.float64)
+    out_ref = case.x[:, :CP].double().clone()
+    out_ref[perm, :C] += sc[perm, None] * y
+    outg = case.out.cpu()
+    err = (outg[:, :CP].double() - out_ref).abs().max().item() / out_ref.abs().max().item()
+    assert err < 1e-4, err
+    assert (outg[:, :C] != SENT).all()
+    assert (outg[:, C:CP] == 0).all() and (outg[:, CP:] == SENT).all()
+    if case.rowscale is not None:   # DropPath scale 0 (sample 0): the residual stream passes bit for bit
+        assert torch.equal(outg[:Hh * Ww, :C], case.x[:Hh * Ww, :C])
+        assert not torch.equal(outg[Hh * Ww:, :C], case.x[Hh * Ww:, :C])
+
+
+@pytest.mark.parametrize("C,hd", [(180, 30), (120, 20)])
+@pytest.mark.parametrize("w_split", [False, True])
+@pytest.mark.parametrize("shift", [0, 4, 3])
+def test_swin_attn_fwd_vs_float64(shift, w_split, C, hd):
+    _check_attn(_AttnCase(C, hd, w_split), shift)
+
+
+def test_swin_attn_fwd_vs_float64_no_rowscale():
+    _check_attn(_AttnCase(180, 30, False, with_scale=False), 4)
+
+
+@pytest.mark.parametrize("bad", [dict(nh=4), dict(Hh=20), dict(shift=8), dict(ldx=190), dict(rows_per_scale=96)])
+def test_swin_attn_fwd_rejects_bad_geometry(bad):
+    """Refused by the argument checks (RuntimeError through _hip.check), and no kernel is launched."""
+    case = _AttnCase(180, 30, False)
+    kw = dict(shift=4)
+    kw.update(bad)
+    H.ktime_begin(8)
+    try:
+        with pytest.raises(RuntimeError, match="swin_attn_fwd"):
+            case.run(**kw)
+    finally:
+        n = H.ktime_end()
+    torch.cuda.synchronize()
+    assert n == 0
+    assert (case.out == SENT).all() and (case.qkv == SENT).all()
+
+
+def _mlp_bwd_case(B, Hh, Ww, shift, dparam_acc, scale, rows_per_scale):
+    """One kair_swin_mlp_bwd call and its float64 restatement.  Every row stride is wider than the packed width
+    (the wrapper passes shape[-1]); the columns past it hold a sentinel that must survive."""
+    C = 180
+    M = B * Hh * Ww
+    g = torch.Generator().manual_seed(23 + shift)
+    dc = torch.full((M, CP + 8), SENT).to(torch.bfloat16)
+    dc[:, :CP] = 0
+    dc[:, :C] = torch.randn(M, C, generator=g).to(torch.bfloat16)
+    gd = torch.full((M, HDP + 8), SENT).to(torch.bfloat16)
+    gd[:, :HDP] = 0
+    gd[:, :HD] = (torch.rand(M, HD, generator=g) * 1.4 - 0.2).to(torch.bfloat16)
+    w1, w2 = 0.05 * torch.randn(HD, C, generator=g), 0.05 * torch.randn(C, HD, generator=g)
+    W1t = _pack(w1, 13, (1, HD, HDP), (1, C, CP))      # as swinir_engine._Lin(..., frag_t=True) packs fc1 / fc2
+    W2t = _pack(w2, 13, (1, C, CP), (1, HD, HDP))
+    x = torch.full((M, CP + 4), SENT)
+    x[:, :CP] = 0
+    x[:, :C] = torch.randn(M, C, generator=g) * 1.5 + 0.3
+    x64 = x[:, :C].double()
+    mean = x64.mean(1).float()
+    rstd = (1.0 / torch.sqrt(x64.var(1, unbiased=False) + 1e-5)).float()
+    gamma = 1 + 0.2 * torch.randn(C, generator=g)
+    D0 = torch.randn(M, CP + 4, generator=g)
+    dg0, db0 = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    du = torch.full((M, HDP + 8), SENT, device=dev, dtype=torch.bfloat16)
+    dco = torch.full((M, CP + 8), SENT, device=dev, dtype=torch.bfloat16)
+    Dd, dgam, dbet = D0.to(dev), dg0.to(dev), db0.to(dev)
+    ws = torch.empty(H.swin_mlp_bwd_ws(), device=dev)
+    args = [gd.to(dev), W2t, W1t, du, x.to(dev), gamma.to(dev), mean.to(dev), rstd.to(dev), C, Dd, dco,
+            scale.to(dev) if scale is not None else None, rows_per_scale, Hh, Ww, shift, dgam, dbet, ws, M, CP, HDP]
+    dc_d = dc.to(dev)
+    H.swin_mlp_bwd(dc_d, *args, dparam_acc=dparam_acc)
+    torch.cuda.synchronize()
+
+    w1b, w2b = w1.to(torch.bfloat16).double(), w2.to(torch.bfloat16).double()
+    # dU = (Dc . W2) * GELU': the bound of test_rowgemm_gpu.py::test_rowgemm_store_and_gate (bf16 output rounding)
+    du_ref = (dc[:, :C].double() @ w2b) * gd[:, :HD].double()
+    dug = du.cpu().double()
+    assert max_err(dug[:, :HD], du_ref) < 8e-3
+    assert (dug[:, HD:HDP] == 0).all() and (dug[:, HDP:] == SENT).all()
+    # D += LN2-backward(dU_stored . W1): the bounds of test_rowgemm_gpu.py::test_rowgemm_lnbwd (D 2e-5, copy 8e-3,
+    # dgamma / dbeta 2e-5, each max-abs error over max-abs reference)
+    gr = dug[:, :HD] @ w1b
+    xh = (x64 - mean.double()[:, None]) * rstd.double()[:, None]
+    gy = gr * gamma.double()
+    dx = rstd.double()[:, None] * (gy - gy.mean(1, keepdim=True) - xh * (gy * xh).mean(1, keepdim=True))
+    Dref = D0.double().clone()
+    Dref[:, :C] += dx
+    Dg = Dd.cpu()
+    assert max_err(Dg[:, :C], Dref[:, :C]) < 2e-5
+    assert torch.equal(Dg[:, C:], D0[:, C:])                                          # pad columns stay what they were
+    perm = win_perm(B, Hh, Ww, 8, shift)
+    sc = scale.double().repeat_interleave(rows_per_scale) if scale is not None else torch.ones(M, dtype=torch.float64)
+    cref = (sc[:, None] * Dref[:, :CP])[perm]                                         # dco[r] = s[token] D[token]
+    dcog = dco.cpu().double()
+    assert max_err(dcog[:, :CP], cref) < 8e-3
+    assert (dcog[:, CP:] == SENT).all()
+    dg_ref, db_ref = (gr * xh).sum(0), gr.sum(0)
+    if dparam_acc:
+        dg_ref, db_ref = dg_ref + dg0.double(), db_ref + db0.double()
+    assert max_err(dgam, dg_ref) < 2e-5
+    assert max_err(dbet, db_ref) < 2e-5
+    return dc_d, args
+
+
+@pytest.mark.parametrize("with_scale", [True, False])
+@pytest.mark.parametrize("dparam_acc", [False, True])
+@pytest.mark.parametrize("shift", [0, 4])
+def test_swin_mlp_bwd_vs_float64(shift, dparam_acc, with_scale):
+    scale = torch.tensor([1.25, 0.0]) if with_scale else None
+    _mlp_bwd_case(2, 16, 24, shift, dparam_acc, scale, 16 * 24)
+
+
+def test_swin_mlp_bwd_second_tile():
+    """The launch is min(M / 64, compute units) persistent workgroups (kair_swin_mlp_bwd, kair_swin_mlp_bwd_ws), so
+    M = 64 (CUs + 1) is the smallest size at which a workgroup runs the loop twice and the LayerNorm backward of a
+    tile overlaps the next tile's GEMM: one image of 8 x 8 (CUs + 1) tokens, a DropPath scale per tile.  16,448 rows
+    on the 256 compute units of an MI355X; the float64 reference takes well under a second."""
+    nt = torch.cuda.get_device_properties(0).multi_processor_count + 1
+    g = torch.Generator().manual_seed(29)
+    scale = torch.rand(nt, generator=g) + 0.5
+    scale[::5] = 0.0
+    _mlp_bwd_case(1, 8, 8 * nt, 4, True, scale, 64)
+
+
+def test_swin_mlp_bwd_rejects_dco_aliasing_dc():
+    dc_d, args = _mlp_bwd_case(1, 8, 8, 0, False, None, 64)
+    args[10] = dc_d                                                                   # dco
+    H.ktime_begin(8)
+    try:
+        with pytest.raises(RuntimeError, match="alias"):
+            H.swin_mlp_bwd(dc_d, *args)
+    finally:
+        n = H.ktime_end()
+    assert n == 0
