@@ -712,6 +712,35 @@ int kair_synth_sr(const float* pool, int C, int Hs, int Ws, const int* params, i
 int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int* params, int B, int PS, float sigma,
                   unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
 
+/* ---- USRNet training data (csrc/synth_usr.hip; DatasetUSRNet.__getitem__, data/dataset_usrnet.py:46-113) --------
+ * kair_usr_gauss_kernels: B blur kernels [B][ksize][ksize] fp32, utils_sisr.gen_kernel (utils_sisr.py:172-215) with
+ * the draws made by the caller.  Sample b reads gpar[b * gstride + {0, 1, 2}] = {lambda1, lambda2, theta} and
+ * kpar[b * kstride + {0, 1, 2, 3}] = {source, bank_idx, sf_k, mode_k}.  Source 0: raw[y][x] = exp(-z^T Sigma^-1 z / 2),
+ * Sigma = Q diag(lambda1, lambda2) Q^T, Q = [[cos, -sin], [sin, cos]](theta), z = (x - mu, y - mu),
+ * mu = ksize / 2 + 0.5 (sf_k - ksize % 2), divided by its sum, then augment mode mode_k (0..7).  Source 1: row bank_idx
+ * of bank [K][ksize][ksize] divided by its sum, not augmented (bank may be null with K = 0: every sample Gaussian).
+ *
+ * kair_synth_usr: params as for kair_synth_dn at stride pstride ints (rnd_* in H coordinates), values clamped into
+ * the pool.  outH [B][C][PS][PS] = the augmented crops; outL [B][C][PS/sf][PS/sf] =
+ *   L0[i][j] = sum_{u, v} k[b][u][v] H[(i sf + kh/2 - u) mod PS][(j sf + kw/2 - v) mod PS]
+ * (ndimage.convolve(mode='wrap') then [0::sf, 0::sf]; true modulo, fp32 fmaf in (u, v) order), then
+ *   L = (trunc8 ? floor(255 L0) / 255 : L0) + sigma[b * sstride] N(0, 1)
+ * with the Philox normals of kair_synth_dn keyed by (seed, step) and the outL element index; sigma null or a zero
+ * entry: nothing added.  k: [B][kh][kw].  direct != 0 forces the one-thread-per-output kernel that the LDS-banded one
+ * falls back to when a kh-row band of the image does not fit in LDS (same bits; for tests).
+ *
+ * kair_usr_degrade: the same L for whole images x [N][C][Hs][Ws] (Hs != Ws allowed, no crop / augment):
+ * outL [N][C][ceil(Hs/sf)][ceil(Ws/sf)]; k at stride kstride floats per sample (0: one kernel for all). */
+int kair_usr_gauss_kernels(const float* gpar, int gstride, const int* kpar, int kstride, const float* bank, int K,
+                           int B, int ksize, float* out, void* stream);
+int kair_synth_usr(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int B, int PS,
+                   int sf, const float* k, int kh, int kw, const float* sigma, int sstride, int trunc8,
+                   unsigned long long seed, unsigned long long step, float* outH, float* outL, int direct,
+                   void* stream);
+int kair_usr_degrade(const float* x, int N, int C, int Hs, int Ws, int sf, const float* k, long kstride, int kh, int kw,
+                     const float* sigma, int sstride, int trunc8, unsigned long long seed, unsigned long long step,
+                     float* outL, int direct, void* stream);
+
 const char* kair_last_error(void);
 int kair_device_arch(char* buf, int len);
 

@@ -214,6 +214,11 @@ _SIGS = {
                       c_vp],
     "kair_synth_dn": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_float, ctypes.c_ulonglong, ctypes.c_ulonglong,
                       c_vp, c_vp, c_vp],
+    "kair_usr_gauss_kernels": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_synth_usr": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                       c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_int, c_vp],
+    "kair_usr_degrade": [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_long, c_int, c_int, c_vp, c_int, c_int,
+                         ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_int, c_vp],
     "kair_swin_attn_fwd": [c_vp, c_long, c_vp, c_vp, c_float, c_int, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_float, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_long, c_long, c_int,
                            c_int, c_int, c_int, c_int, c_vp],
@@ -930,6 +935,79 @@ def synth_dn(pool, params, B, PS, sigma, seed, step, outH, outL):
     N, C, Hs, Ws = pool.shape
     check(lib().kair_synth_dn(ptr(pool), C, Hs, Ws, ptr(params), B, PS, sigma, seed, step, ptr(outH), ptr(outL),
                               stream_ptr()), "synth_dn")
+
+
+def _rows_of(t, dtype, ncol, what):
+    """(pointer, row stride) of a [B, >= ncol] parameter table; a column slice of a wider table is fine."""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] < ncol or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: expected a [B, >= {ncol}] {dtype} table with unit column stride")
+    return ptr(t), t.stride(0)
+
+
+def usr_gauss_kernels(gpar, kpar, bank, out):
+    """out [B, 1, ks, ks] <- the blur kernels of gpar [B, 3] {lambda1, lambda2, theta} and kpar [B, 4]
+    {source, bank_idx, sf_k, mode_k}; bank [K, ks, ks] or None (kair_usr_gauss_kernels)."""
+    require_device(gpar, kpar, bank, out)
+    B, ks = out.shape[0], out.shape[-1]
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape[-2] != ks or out.numel() != B * ks * ks:
+        raise ValueError("usr_gauss_kernels: out must be a contiguous fp32 [B, 1, ks, ks]")
+    if gpar.shape[0] < B or kpar.shape[0] < B:
+        raise ValueError("usr_gauss_kernels: fewer parameter rows than kernels")
+    K = 0
+    if bank is not None:
+        if bank.dtype != torch.float32 or not bank.is_contiguous() or tuple(bank.shape[-2:]) != (ks, ks):
+            raise ValueError("usr_gauss_kernels: bank must be a contiguous fp32 [K, ks, ks]")
+        K = bank.numel() // (ks * ks)
+    gp, gs = _rows_of(gpar, torch.float32, 3, "usr_gauss_kernels gpar")
+    kp, kst = _rows_of(kpar, torch.int32, 4, "usr_gauss_kernels kpar")
+    check(lib().kair_usr_gauss_kernels(gp, gs, kp, kst, ptr(bank), K, B, ks, ptr(out), stream_ptr()),
+          "usr_gauss_kernels")
+
+
+def _usr_sigma(sigma, B, what):
+    if sigma is None:
+        return None, 0
+    if sigma.dtype != torch.float32 or sigma.dim() != 1 or sigma.shape[0] < B:
+        raise ValueError(f"{what}: sigma must be an fp32 vector of B entries (a column of a wider table is fine)")
+    return ptr(sigma), sigma.stride(0)
+
+
+def synth_usr(pool, params, B, PS, sf, k, sigma, trunc8, seed, step, outH, outL, direct=False):
+    """USRNet batch (kair_synth_usr): params [B, >= 4] int32 {image, rnd_h, rnd_w, mode}, k [B, 1, kh, kw],
+    sigma fp32 [B] or None (noise off)."""
+    require_device(pool, params, k, sigma, outH, outL)
+    N, C, Hs, Ws = pool.shape
+    kh, kw = k.shape[-2:]
+    ls = PS // sf
+    if pool.dtype != torch.float32 or not pool.is_contiguous() or k.dtype != torch.float32 or not k.is_contiguous() \
+            or k.numel() != B * kh * kw:
+        raise ValueError("synth_usr: pool / k must be contiguous fp32, k [B, 1, kh, kw]")
+    if params.shape[0] < B:
+        raise ValueError("synth_usr: fewer parameter rows than samples")
+    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C, ls, ls))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f"synth_usr: output must be a contiguous fp32 {shp}")
+    pp, ps = _rows_of(params, torch.int32, 4, "synth_usr params")
+    sp, ss = _usr_sigma(sigma, B, "synth_usr")
+    check(lib().kair_synth_usr(ptr(pool), N, C, Hs, Ws, pp, ps, B, PS, sf, ptr(k), kh, kw, sp, ss, int(trunc8), seed, step,
+                               ptr(outH), ptr(outL), int(direct), stream_ptr()), "synth_usr")
+
+
+def usr_degrade(x, k, sf, sigma, trunc8, seed, step, outL, direct=False):
+    """L of whole images x [N, C, Hs, Ws] (kair_usr_degrade): k [N, 1, kh, kw] or one [kh, kw] kernel for all."""
+    require_device(x, k, sigma, outL)
+    N, C, Hs, Ws = x.shape
+    kh, kw = k.shape[-2:]
+    if x.dtype != torch.float32 or not x.is_contiguous() or k.dtype != torch.float32 or not k.is_contiguous() \
+            or k.numel() not in (kh * kw, N * kh * kw):
+        raise ValueError("usr_degrade: x / k must be contiguous fp32, k [N, 1, kh, kw] or [kh, kw]")
+    shp = (N, C, -(-Hs // sf), -(-Ws // sf))
+    if outL.dtype != torch.float32 or not outL.is_contiguous() or tuple(outL.shape) != shp:
+        raise ValueError(f"usr_degrade: output must be a contiguous fp32 {shp}")
+    sp, ss = _usr_sigma(sigma, N, "usr_degrade")
+    kstride = 0 if k.numel() == kh * kw else kh * kw
+    check(lib().kair_usr_degrade(ptr(x), N, C, Hs, Ws, sf, ptr(k), kstride, kh, kw, sp, ss, int(trunc8), seed, step,
+                                 ptr(outL), int(direct), stream_ptr()), "usr_degrade")
 
 
 def swin_attn_fwd(x, ldx, gamma, beta, eps, C, ln, ldln, mean, rstd, wqkv, bqkv, qkv, table, scale, O, ldo, o_ones_col,

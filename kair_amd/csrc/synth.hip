@@ -4,24 +4,15 @@
 //   DatasetDnCNN.__getitem__ data/dataset_dncnn.py:50-75 (random crop, 8-way augment, L = H + sigma N)
 // for a whole batch in one launch, reading an image pool resident in HBM (fp32 NCHW, [0, 1]).
 //
-// Augment modes (utils_image.augment_img, utils_image.py:387-405) are the 8 dihedral maps of a
-// square n x n patch: out(i, j) = src(si, sj) with (p, q) = mode&1 ? (j, i) : (i, j),
-// si = mode&2 ? n-1-p : p, sj = mode&4 ? n-1-q : q  (checked mode by mode against the numpy code).
+// The 8 augment modes: aug_src in synth_common.h.
 // Bicubic: separable taps per output row / column (weights and symmetric-reflected source indices
 // from calculate_weights_indices, utils_image.py:880-932, built on the host), summed rows-first then
 // columns as imresize does (utils_image.py:938-1005).  AWGN: Philox-4x32-10 keyed by (seed, step),
 // counter = element index, Box-Muller -- no bitwise pin to torch's CPU generator is possible (or
 // meaningful); tests check the noise statistically.
-#include "common.h"
+#include "synth_common.h"
 
 namespace {
-
-KAIR_DEV void aug_src(int mode, int i, int j, int n, int& si, int& sj) {
-  int p = i, q = j;
-  if (mode & 1) { p = j; q = i; }
-  si = (mode & 2) ? n - 1 - p : p;
-  sj = (mode & 4) ? n - 1 - q : q;
-}
 
 // one thread per output element: [0, nH) -> H patch elements, [nH, nH + nL) -> L patch elements
 __global__ __launch_bounds__(256) void synth_sr_kernel(const float* __restrict__ pool, int C, int Hs, int Ws,
@@ -134,28 +125,6 @@ __global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restri
     for (int bq = 0; bq < P; ++bq) acc = fmaf(ww[gx * P + bq], sV[(si - r0) * Wmax + iw[gx * P + bq] - lo], acc);
     oL[i * LS + j] = acc;
   }
-}
-
-// Philox-4x32-10 (Salmon et al., SC'11)
-KAIR_DEV uint4 philox(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * ctr.x;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * ctr.z;
-    const unsigned h0 = (unsigned)(p0 >> 32), l0 = (unsigned)p0, h1 = (unsigned)(p1 >> 32), l1 = (unsigned)p1;
-    ctr = make_uint4(h1 ^ ctr.y ^ key.x, l1, h0 ^ ctr.w ^ key.y, l0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
-KAIR_DEV float normal_at(unsigned long long idx, unsigned long long seed, unsigned long long step) {
-  const uint4 r = philox(make_uint4((unsigned)idx, (unsigned)(idx >> 32), (unsigned)step, (unsigned)(step >> 32)),
-                         make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-  const float u1 = ((r.x >> 8) + 1) * (1.0f / 16777216.0f);   // (0, 1]
-  const float u2 = (r.y >> 8) * (1.0f / 16777216.0f);         // [0, 1)
-  return sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }
 
 // H = aug(crop(pool)); L = H + sigma * N(0, 1)   (sigma already divided by 255)

@@ -10,7 +10,25 @@ rank-strided slice of it), then per sample random.randint for the crop rows / co
 augment mode in the order __getitem__ draws them (data/dataset_sr.py:78-91,
 data/dataset_dncnn.py:59-66).  The per-sample geometry is drawn on the host (a few ints), the
 pixels are produced on the device (kair_synth_sr / kair_synth_dn in csrc/synth.hip).
+
+task="usrnet" makes DatasetUSRNet batches (data/dataset_usrnet.py:46-113) the same way:
+
+    synth = PatchSynth(pool, task="usrnet", H_size=96, scales=[1, 2, 3, 4], sigma_max=25, seed=0)
+    L, H, k, sf, sigma = synth.next(48)          # k [B, 1, 25, 25], sf an int, sigma [B, 1, 1, 1]
+    model.feed_data(synth.next_dict(48))         # the dict ModelPlain4.feed_data reads
+
+Per batch one scale factor from `scales` (dataset_usrnet.py:54-58); per sample, in this order, the image, rnd_h,
+rnd_w, the augment mode, the kernel draw r in [0, 8) (r > 3 and a kernel bank present: a uniform bank row;
+otherwise a Gaussian with lambda_1, lambda_2 ~ U(0.6, 12), theta ~ U(0, pi), sf_k from [1, 2, 3, 4], augment mode_k)
+and the noise level (0 with probability 1/8, else randint(0, sigma_max - 1) / 255).  The reference's motion-blur
+branch (utils_deblur.blurkernel_synthesis) is not built; `kernel_bank` ([K, ks, ks], e.g. exported motion kernels)
+stands in for it, and without a bank every kernel is Gaussian.  The kernels (kair_usr_gauss_kernels) and the batch
+(kair_synth_usr: crop, augment, circular blur, [0::sf] decimation, AWGN) are two launches of csrc/synth_usr.hip.
+`last_params` is then the [B, 12] int32 table that went up: columns 0-3 {image, rnd_h, rnd_w, mode}, 4-7
+{kernel source (0 Gaussian, 1 bank), bank_idx, sf_k, mode_k}, 8-11 the float32 bits of {lambda_1, lambda_2, theta,
+sigma} (`last_params[:, 8:].view(torch.float32)`).
 """
+import math
 import random
 
 import torch
@@ -20,10 +38,25 @@ from ..utils import utils_image as util
 
 
 class PatchSynth:
-    def __init__(self, pool, task="sr", scale=4, H_size=96, sigma=25, seed=0, rank=0, world=1):
+    def __init__(self, pool, task="sr", scale=4, H_size=96, sigma=25, seed=0, rank=0, world=1, scales=(1, 2, 3, 4),
+                 sigma_max=25, kernel_size=25, kernel_bank=None, trunc8=False):
         if pool.dim() != 4 or not pool.is_cuda:
             raise ValueError("PatchSynth: pool must be a device tensor [N, C, Hs, Ws]")
         self.task = task
+        if task == "usrnet":
+            self.scales = [int(s) for s in scales]
+            bad = [s for s in self.scales if s < 1 or H_size % s]
+            if not self.scales or bad:
+                raise ValueError(f"PatchSynth: H_size {H_size} is not divisible by the scales {bad or self.scales}")
+            self.sigma_max, self.ks, self.trunc8 = int(sigma_max), int(kernel_size), bool(trunc8)
+            if self.sigma_max < 1 or self.ks < 1:
+                raise ValueError("PatchSynth: sigma_max and kernel_size must be positive")
+            self.bank = None
+            if kernel_bank is not None:
+                bank = torch.as_tensor(kernel_bank).to(pool.device, torch.float32).contiguous()
+                if bank.dim() != 3 or tuple(bank.shape[-2:]) != (self.ks, self.ks):
+                    raise ValueError(f"PatchSynth: kernel_bank must be [K, {self.ks}, {self.ks}]")
+                self.bank = bank
         self.sf = scale if task == "sr" else 1
         Hs, Ws = pool.shape[-2:]
         if task == "sr":   # modcrop (dataset_sr.py:51)
@@ -45,7 +78,7 @@ class PatchSynth:
             iw, ww = util.bicubic_taps(self.Ws, self.Ws // self.sf, 1.0 / self.sf)
             self.taps_h = (ih.to(dev), wh.to(dev))
             self.taps_w = (iw.to(dev), ww.to(dev))
-        elif task != "dn":
+        elif task not in ("dn", "usrnet"):
             raise ValueError(task)
         self._par_host = None
         self._par_ev = None
@@ -77,7 +110,9 @@ class PatchSynth:
     def next(self, B, out=None):
         """The next batch (L, H), produced on the current stream.  The per-sample geometry goes up
         through a pinned staging buffer with an async copy, so a training loop that calls next()
-        every step never blocks the host on the device."""
+        every step never blocks the host on the device.  task "usrnet": (L, H, k, sf, sigma)."""
+        if self.task == "usrnet":
+            return self._next_usr(B)
         dev = self.pool.device
         host = self.draw(B)
         if self._par_host is None or self._par_host.shape[0] < B:
@@ -102,6 +137,61 @@ class PatchSynth:
         self.step += 1
         self.last_params = par
         return Lp, Hp
+
+    def _draw_usr(self, B):
+        """Host draws of the next USRNet batch: (sf, [B, 12] int32 table; see the module docstring)."""
+        sf = self.rng.choice(self.scales)
+        ints = torch.zeros(B, 12, dtype=torch.int32)
+        flts = torch.zeros(B, 4, dtype=torch.float32)
+        K = 0 if self.bank is None else self.bank.shape[0]
+        for b in range(B):
+            img = self._next_index()
+            rh = self.rng.randint(0, self.Hs - self.PS)
+            rw = self.rng.randint(0, self.Ws - self.PS)
+            mode = self.rng.randint(0, 7)
+            row = [img, rh, rw, mode, 0, 0, 1, 0]
+            if self.rng.randint(0, 7) > 3 and K:
+                row[4], row[5] = 1, self.rng.randint(0, K - 1)
+            else:
+                flts[b, 0] = self.rng.uniform(0.6, 12.0)
+                flts[b, 1] = self.rng.uniform(0.6, 12.0)
+                flts[b, 2] = self.rng.uniform(0.0, math.pi)
+                row[6] = self.rng.choice([1, 2, 3, 4])
+                row[7] = self.rng.randint(0, 7)
+            if self.rng.randint(0, 7) != 1:
+                flts[b, 3] = self.rng.randint(0, self.sigma_max - 1) / 255.0
+            ints[b, :8] = torch.tensor(row, dtype=torch.int32)
+        ints[:, 8:] = flts.view(torch.int32)
+        return sf, ints
+
+    def _next_usr(self, B):
+        dev = self.pool.device
+        sf, host = self._draw_usr(B)
+        if self._par_host is None or self._par_host.shape[0] < B:
+            self._par_host = torch.empty(B, 12, dtype=torch.int32).pin_memory()
+            self._par_ev = None
+        if self._par_ev is not None:
+            self._par_ev.synchronize()   # the previous batch's copy has read the staging buffer
+        self._par_host[:B].copy_(host)
+        par = self._par_host[:B].to(dev, non_blocking=True)
+        self._par_ev = torch.cuda.Event()
+        self._par_ev.record()
+        fl = par[:, 8:].view(torch.float32)
+        k = torch.empty(B, 1, self.ks, self.ks, device=dev)
+        Hp = torch.empty(B, self.C, self.PS, self.PS, device=dev)
+        Lp = torch.empty(B, self.C, self.PS // sf, self.PS // sf, device=dev)
+        H.usr_gauss_kernels(fl, par[:, 4:8], self.bank, k)
+        H.synth_usr(self.pool, par, B, self.PS, sf, k, fl[:, 3], self.trunc8, self.seed, self.step, Hp, Lp)
+        self.step += 1
+        self.last_params = par
+        return Lp, Hp, k, sf, fl[:, 3].reshape(B, 1, 1, 1).contiguous()
+
+    def next_dict(self, B):
+        """The next USRNet batch as the dict ModelPlain4.feed_data reads (sf an int64 tensor [B])."""
+        if self.task != "usrnet":
+            raise ValueError("PatchSynth.next_dict: task 'usrnet' only")
+        L, Hh, k, sf, sigma = self._next_usr(B)
+        return {"L": L, "H": Hh, "k": k, "sf": torch.full((B,), sf, dtype=torch.int64), "sigma": sigma}
 
 
 def synthetic_pool(N, C, Hs, Ws, seed=0, device="cuda"):

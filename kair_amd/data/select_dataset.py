@@ -1,5 +1,6 @@
 """Dataset factory (mirror of /root/reference/data/select_dataset.py:12-100) for the datasets that
-feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1) and 'sr' (DatasetSR, configs 2/4/5).
+feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1), 'sr' (DatasetSR, configs 2/4/5) and
+'usrnet' (DatasetUSRNet, config 3).
 Other dataset types are off the path and raise NotImplementedError naming the type."""
 
 
@@ -9,6 +10,8 @@ def define_Dataset(dataset_opt):
         from .dataset_dncnn import DatasetDnCNN as D
     elif t in ("sr", "super-resolution"):
         from .dataset_sr import DatasetSR as D
+    elif t == "usrnet":
+        from .dataset_usrnet import DatasetUSRNet as D
     else:
-        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr).")
+        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr, usrnet).")
     return D(dataset_opt)
