@@ -741,6 +741,35 @@ int kair_usr_degrade(const float* x, int N, int C, int Hs, int Ws, int sf, const
                      const float* sigma, int sstride, int trunc8, unsigned long long seed, unsigned long long step,
                      float* outL, int direct, void* stream);
 
+/* ---- JPEG CAR training data (csrc/synth_jpeg.hip; DatasetJPEG.__getitem__, data/dataset_jpeg.py:40-96) ----------
+ * The lossy part of a baseline JPEG encode + decode in libjpeg's 32-bit integer arithmetic (jfdctint / jidctint,
+ * Annex-K tables scaled by the quality, force_baseline), bit-equal to the decoder's pixels; the entropy coding, which
+ * is lossless, is left out.  utils/utils_jpeg.py states the same arithmetic in numpy.
+ *
+ * kair_jpeg_roundtrip: x, out [N][C][H][W] fp32 in [0, 1]; samples are rint(255 clamp(x, 0, 1)), out = decoded / 255.
+ * C 1: a gray JPEG.  C 3: RGB as YCbCr 4:2:0, decoded with the h2v2 "fancy" upsampler; W >= 5 (libjpeg switches
+ * upsampler below that) and `workspace` of kair_jpeg_workspace_bytes(N, C, H, W) bytes, 8-byte aligned (the decoded
+ * planes; may be null for C 1).  quality: device ints read at quality[n * qstride] (qstride 0: one for all), clamped to
+ * 1..100.
+ *
+ * kair_rgb2gray8: x [N][3][H][W] fp32 -> out [N][1][H][W] = gray(uint8 triple) / 255.  mode 0: utils_image.rgb2ycbcr
+ * (only_y) on uint8, 16 + round((65.481 R + 128.553 G + 24.966 B) / 255), an exact tie (194 of the 2^24 triples)
+ * rounding up; mode 1: OpenCV's COLOR_RGB2GRAY, (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ *
+ * kair_synth_jpeg: a batch of DatasetJPEG training items from pool [N][C][Hs][Ws] (Hs, Ws >= PS + 8).  Sample b reads
+ * params[b * pstride + {0..7}] = {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2, rw2} (values clamped into range):
+ * the (PS + 8)^2 crop at (rnd_h, rnd_w), augment mode 0..7, uint8; is_color 0: gray by gray_mode (kair_rgb2gray8's
+ * modes; a 1-channel pool is used as it is) and a gray JPEG, is_color 1 (C 3): a colour JPEG; the block grid starts
+ * at the crop's corner.  outH / outL [B][is_color ? 3 : 1][PS][PS] = the uncompressed / decoded patch at
+ * [rh2 : rh2 + PS, rw2 : rw2 + PS] (rh2, rw2 in 0..8), / 255.  A colour patch is decoded in LDS by one workgroup per
+ * sample, which holds PS + 8 up to 272; a larger colour patch is an argument error. */
+long kair_jpeg_workspace_bytes(int N, int C, int H, int W);
+int kair_jpeg_roundtrip(const float* x, int N, int C, int H, int W, const int* quality, int qstride, float* out,
+                        void* workspace, void* stream);
+int kair_rgb2gray8(const float* x, int N, int H, int W, int mode, float* out, void* stream);
+int kair_synth_jpeg(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int B, int PS,
+                    int is_color, float* outH, float* outL, void* stream);
+
 const char* kair_last_error(void);
 int kair_device_arch(char* buf, int len);
 

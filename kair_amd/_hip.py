@@ -219,6 +219,10 @@ _SIGS = {
                        c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_int, c_vp],
     "kair_usr_degrade": [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_long, c_int, c_int, c_vp, c_int, c_int,
                          ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_int, c_vp],
+    "kair_jpeg_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "kair_jpeg_roundtrip": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp],
+    "kair_rgb2gray8": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_synth_jpeg": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "kair_swin_attn_fwd": [c_vp, c_long, c_vp, c_vp, c_float, c_int, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_float, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_long, c_long, c_int,
                            c_int, c_int, c_int, c_int, c_vp],
@@ -245,7 +249,8 @@ _SIGS = {
 }
 _RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
-            "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long}
+            "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
+            "kair_jpeg_workspace_bytes": c_long}
 
 _lib = None
 
@@ -1008,6 +1013,55 @@ def usr_degrade(x, k, sf, sigma, trunc8, seed, step, outL, direct=False):
     kstride = 0 if k.numel() == kh * kw else kh * kw
     check(lib().kair_usr_degrade(ptr(x), N, C, Hs, Ws, sf, ptr(k), kstride, kh, kw, sp, ss, int(trunc8), seed, step,
                                  ptr(outL), int(direct), stream_ptr()), "usr_degrade")
+
+
+def jpeg_roundtrip(x, quality, out):
+    """out <- the JPEG round trip of x [N, 1 or 3, H, W] fp32 in [0, 1] (kair_jpeg_roundtrip); quality: device int32,
+    one entry for all samples or N entries.  Returns the error code of a refused call through RuntimeError."""
+    require_device(x, quality, out)
+    N, C, Hh, W = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.shape != x.shape:
+        raise ValueError("jpeg_roundtrip: x / out must be contiguous fp32 of one shape")
+    if quality.dtype != torch.int32 or quality.dim() != 1 or quality.shape[0] not in (1, N):
+        raise ValueError("jpeg_roundtrip: quality must be an int32 vector of 1 or N entries")
+    qstride = 0 if quality.shape[0] == 1 else quality.stride(0)
+    ws = None
+    if C == 3 and W >= 5:
+        nbytes = lib().kair_jpeg_workspace_bytes(N, C, Hh, W)
+        if nbytes < 0:
+            raise ValueError("jpeg_roundtrip: image too large")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    check(lib().kair_jpeg_roundtrip(ptr(x), N, C, Hh, W, ptr(quality), qstride, ptr(out), ptr(ws), stream_ptr()),
+          "jpeg_roundtrip")
+
+
+def rgb2gray8(x, mode, out):
+    """out [N, 1, H, W] <- gray uint8 / 255 of x [N, 3, H, W] (kair_rgb2gray8): mode 0 rgb2ycbcr Y, mode 1 OpenCV."""
+    require_device(x, out)
+    N, C, Hh, W = x.shape
+    if C != 3 or x.dtype != torch.float32 or not x.is_contiguous() or out.dtype != torch.float32 \
+            or not out.is_contiguous() or tuple(out.shape) != (N, 1, Hh, W):
+        raise ValueError("rgb2gray8: x must be a contiguous fp32 [N, 3, H, W], out [N, 1, H, W]")
+    check(lib().kair_rgb2gray8(ptr(x), N, Hh, W, int(mode), ptr(out), stream_ptr()), "rgb2gray8")
+
+
+def synth_jpeg(pool, params, B, PS, is_color, outH, outL):
+    """JPEG CAR batch (kair_synth_jpeg): params [B, >= 8] int32 {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2,
+    rw2}; outH / outL [B, 3 if is_color else 1, PS, PS]."""
+    require_device(pool, params, outH, outL)
+    N, C, Hs, Ws = pool.shape
+    if pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise ValueError("synth_jpeg: pool must be contiguous fp32")
+    if params.shape[0] < B:
+        raise ValueError("synth_jpeg: fewer parameter rows than samples")
+    shp = (B, 3 if is_color else 1, PS, PS)
+    for t in (outH, outL):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f"synth_jpeg: output must be a contiguous fp32 {shp}")
+    pp, ps = _rows_of(params, torch.int32, 8, "synth_jpeg params")
+    check(lib().kair_synth_jpeg(ptr(pool), N, C, Hs, Ws, pp, ps, B, PS, int(bool(is_color)), ptr(outH), ptr(outL),
+                                stream_ptr()), "synth_jpeg")
 
 
 def swin_attn_fwd(x, ldx, gamma, beta, eps, C, ln, ldln, mean, rstd, wqkv, bqkv, qkv, table, scale, O, ldo, o_ones_col,

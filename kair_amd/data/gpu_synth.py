@@ -27,6 +27,18 @@ stands in for it, and without a bank every kernel is Gaussian.  The kernels (kai
 `last_params` is then the [B, 12] int32 table that went up: columns 0-3 {image, rnd_h, rnd_w, mode}, 4-7
 {kernel source (0 Gaussian, 1 bank), bank_idx, sf_k, mode_k}, 8-11 the float32 bits of {lambda_1, lambda_2, theta,
 sigma} (`last_params[:, 8:].view(torch.float32)`).
+
+task="jpeg" makes DatasetJPEG batches (data/dataset_jpeg.py:40-96) for the JPEG artifact-reduction SwinIR:
+
+    synth = PatchSynth(pool, task="jpeg", H_size=126, quality_factor=40, is_color=False, seed=0)
+    L, H = synth.next(8)                         # [B, 1 (or 3 with is_color), 126, 126]
+
+Per sample, in this order: the image, rnd_h and rnd_w of the (H_size + 8)^2 crop, the augment mode, the gray conversion
+(not with is_color; random() > 0.5: rgb2ycbcr Y, mode 0, else OpenCV's RGB2GRAY, mode 1), the quality (an int as in the
+reference, or a list to draw from uniformly: blind CAR, an extension) and one random() > 0.5 that decides whether the
+second H_size^2 crop sits at random offsets rh2, rw2 in [0, 8] or at (0, 0).  One launch (kair_synth_jpeg,
+csrc/synth_jpeg.hip) does the crop, augment, uint8 and gray conversion, the JPEG round trip and the second crop.
+`last_params` is the [B, 8] int32 table {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2, rw2}.
 """
 import math
 import random
@@ -39,7 +51,7 @@ from ..utils import utils_image as util
 
 class PatchSynth:
     def __init__(self, pool, task="sr", scale=4, H_size=96, sigma=25, seed=0, rank=0, world=1, scales=(1, 2, 3, 4),
-                 sigma_max=25, kernel_size=25, kernel_bank=None, trunc8=False):
+                 sigma_max=25, kernel_size=25, kernel_bank=None, trunc8=False, quality_factor=40, is_color=False):
         if pool.dim() != 4 or not pool.is_cuda:
             raise ValueError("PatchSynth: pool must be a device tensor [N, C, Hs, Ws]")
         self.task = task
@@ -57,6 +69,16 @@ class PatchSynth:
                 if bank.dim() != 3 or tuple(bank.shape[-2:]) != (self.ks, self.ks):
                     raise ValueError(f"PatchSynth: kernel_bank must be [K, {self.ks}, {self.ks}]")
                 self.bank = bank
+        if task == "jpeg":
+            self.qualities = [int(quality_factor)] if isinstance(quality_factor, int) else [int(q) for q in quality_factor]
+            if not self.qualities or any(q < 1 or q > 100 for q in self.qualities):
+                raise ValueError("PatchSynth: quality_factor must be an int or a list of ints in 1..100")
+            self.q_drawn = not isinstance(quality_factor, int)   # an int (the reference's option) costs no draw
+            self.is_color = bool(is_color)
+            if pool.shape[1] not in (1, 3) or (self.is_color and pool.shape[1] != 3):
+                raise ValueError("PatchSynth: task 'jpeg' needs a 1- or 3-channel pool (3 with is_color)")
+            if H_size + 8 > min(pool.shape[-2:]):
+                raise ValueError(f"PatchSynth: task 'jpeg' crops H_size + 8 = {H_size + 8}; the pool images are smaller")
         self.sf = scale if task == "sr" else 1
         Hs, Ws = pool.shape[-2:]
         if task == "sr":   # modcrop (dataset_sr.py:51)
@@ -78,7 +100,7 @@ class PatchSynth:
             iw, ww = util.bicubic_taps(self.Ws, self.Ws // self.sf, 1.0 / self.sf)
             self.taps_h = (ih.to(dev), wh.to(dev))
             self.taps_w = (iw.to(dev), ww.to(dev))
-        elif task not in ("dn", "usrnet"):
+        elif task not in ("dn", "usrnet", "jpeg"):
             raise ValueError(task)
         self._par_host = None
         self._par_ev = None
@@ -114,9 +136,10 @@ class PatchSynth:
         if self.task == "usrnet":
             return self._next_usr(B)
         dev = self.pool.device
-        host = self.draw(B)
+        jpeg = self.task == "jpeg"
+        host = self._draw_jpeg(B) if jpeg else self.draw(B)
         if self._par_host is None or self._par_host.shape[0] < B:
-            self._par_host = torch.empty(B, 4, dtype=torch.int32).pin_memory()
+            self._par_host = torch.empty(B, host.shape[1], dtype=torch.int32).pin_memory()
             self._par_ev = None
         if self._par_ev is not None:
             self._par_ev.synchronize()   # the previous batch's copy has read the staging buffer
@@ -125,18 +148,39 @@ class PatchSynth:
         self._par_ev = torch.cuda.Event()
         self._par_ev.record()
         ls = self.PS // self.sf
+        Co = (3 if self.is_color else 1) if jpeg else self.C
         if out is None:
-            Hp = torch.empty(B, self.C, self.PS, self.PS, device=dev)
-            Lp = torch.empty(B, self.C, ls, ls, device=dev)
+            Hp = torch.empty(B, Co, self.PS, self.PS, device=dev)
+            Lp = torch.empty(B, Co, ls, ls, device=dev)
         else:
             Lp, Hp = out
-        if self.task == "sr":
+        if jpeg:
+            H.synth_jpeg(self.pool, par, B, self.PS, self.is_color, Hp, Lp)
+        elif self.task == "sr":
             H.synth_sr(self.pool, par, B, self.PS, self.sf, self.taps_h, self.taps_w, Hp, Lp)
         else:
             H.synth_dn(self.pool, par, B, self.PS, self.sigma, self.seed, self.step, Hp, Lp)
         self.step += 1
         self.last_params = par
         return Lp, Hp
+
+    def _draw_jpeg(self, B):
+        """Host draws of the next JPEG batch: [B, 8] int32 {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2, rw2}."""
+        rows = []
+        for _ in range(B):
+            img = self._next_index()
+            rh = self.rng.randint(0, max(0, self.Hs - self.PS - 8))
+            rw = self.rng.randint(0, max(0, self.Ws - self.PS - 8))
+            mode = self.rng.randint(0, 7)
+            gray_mode = 0
+            if not self.is_color:
+                gray_mode = 0 if self.rng.random() > 0.5 else 1
+            q = self.rng.choice(self.qualities) if self.q_drawn else self.qualities[0]
+            rh2 = rw2 = 0
+            if self.rng.random() > 0.5:
+                rh2, rw2 = self.rng.randint(0, 8), self.rng.randint(0, 8)
+            rows.append((img, rh, rw, mode, gray_mode, q, rh2, rw2))
+        return torch.tensor(rows, dtype=torch.int32)
 
     def _draw_usr(self, B):
         """Host draws of the next USRNet batch: (sf, [B, 12] int32 table; see the module docstring)."""

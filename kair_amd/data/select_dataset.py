@@ -1,6 +1,7 @@
 """Dataset factory (mirror of /root/reference/data/select_dataset.py:12-100) for the datasets that
-feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1), 'sr' (DatasetSR, configs 2/4/5) and
-'usrnet' (DatasetUSRNet, config 3).
+feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1), 'sr' (DatasetSR, configs 2/4/5),
+'usrnet' (DatasetUSRNet, config 3) and 'jpeg' (DatasetJPEG, the JPEG artifact-reduction SwinIR of
+train_swinir_car_jpeg.json).
 Other dataset types are off the path and raise NotImplementedError naming the type."""
 
 
@@ -12,6 +13,8 @@ def define_Dataset(dataset_opt):
         from .dataset_sr import DatasetSR as D
     elif t == "usrnet":
         from .dataset_usrnet import DatasetUSRNet as D
+    elif t == "jpeg":
+        from .dataset_jpeg import DatasetJPEG as D
     else:
-        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr, usrnet).")
+        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr, usrnet, jpeg).")
     return D(dataset_opt)
