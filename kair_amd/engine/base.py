@@ -1,0 +1,319 @@
+"""The step-program protocol: what FusedTrainer, the nn.Module wrappers and the autograd Functions expect of an
+engine, and the plumbing every engine shares.
+
+An engine is the launch sequence of one network over preallocated HBM buffers ("plans", plans.py).  Its drivers use
+  forward(x, ...) -> the output buffer; sets `cur`, the plan the backward reads
+  backward_from_loss(H, grads, loss_weight, charb_eps) -> the device loss [1]    (FusedTrainer)
+  backward_from_grad(gE, grads)                                                  (the autograd Functions)
+  cur, plan_mode, _packed_version (reset by whoever changes the weights), repack_always
+  blocks (objects with a drop-path rate .dp; empty without stochastic depth), drop_path_scales()
+  x3, x3_backoff(), X3_AEXP / x3_gexp_off / x3_backoffs: the fp32x3 range guard
+  seg_hook, and grad_segments() where the engine reports gradient segments (data-parallel buckets)
+EngineBase holds all of it but the three launch sequences; ConvEngineBase adds the conv-net helpers.
+"""
+import math
+import weakref
+
+import torch
+
+from .. import _hip as H
+from .plans import Lease, PlanPool, autograd_mode, plan_mode
+
+
+def _rup(x, m):
+    return (x + m - 1) // m * m
+
+
+class _Conv:
+    """A 3x3 conv's packed forms: forward [Cop][9*Cip] and input-gradient [Cip][9*Cop].
+
+    split (bf16 engines): the forward form holds a hi/lo bf16 pair per weight (pack kind 9,
+    kair_operand.w_split), so the forward product sees the fp32 master weight to ~16 bits.  Plain
+    bf16 weight rounding shifts every output pixel by the same sum(dW * a) and biases PSNR
+    (DESIGN.md "parity at bf16"); activation rounding is unbiased and averages out."""
+
+    def __init__(self, eng, mod, Cop, Cip, need_dgrad=True, split=None, n_perm=0, tied_in=False, fwd_cip=None,
+                 narrow=False, wr=False):
+        """n_perm = r*r: output channels stored sub-pixel-major for a following PixelShuffle(r)
+        (kair_wmap.n_perm; the KAIR_OUT_PSHUF_SPM / PUNSHUF_SPM epilogues store 16 bytes at a time).
+        tied_in: the forward form repeats the input channels in both halves of Cip (kair_wmap kG = 2),
+        for an input held as a hi/lo pair in channels [0, Ci) and [Cip/2, Cip/2 + Ci)
+        (kair_image_to_nhwc_hilo); the weight gradient keeps the plain map (the hi channels).
+        fwd_cip: the forward form's packed input width when it differs from Cip (a [hi | lo] pair image of
+        2 x Cip channels read through tied weights: the SwinIR tail under split_act).
+        narrow: a 64 -> NR <= 4 conv run by the narrow-output kernels (kair_conv3x3_narrow_*): its forward
+        form is pack kind 15 (16x16x32 fragment order, hi/lo halves), the backward reads the fp32 weight.
+        wr: a 192 -> 192 conv also packed for kair_conv3x3_wr: forward pack kind 15, input gradient kind 16
+        (fp32x3: kair_conv3x3_wr_x3's fp16 pairs, kinds 22 / 23)."""
+        self.w, self.b = mod.weight, mod.bias
+        Co, Ci = self.w.shape[:2]
+        self.Co, self.Ci, self.Cop, self.Cip = Co, Ci, Cop, Cip
+        if split is None:
+            split = getattr(eng, "split_conv", False)
+        x3 = eng.x3
+        self.split = (bool(split) and eng.tdt == torch.bfloat16) or x3
+        self.x3 = x3
+        self.n_perm = n_perm
+        self.map = H.wmap(1, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
+        fcip = fwd_cip or Cip
+        self.fcip = fcip
+        kf_grp = (2, Ci, fcip // 2) if tied_in else (1, Ci, Cip)
+        self.mapf = H.wmap(9 if self.split else 1, Co, Ci, (1, Co, Cop), kf_grp, n_perm=n_perm)
+        self.mapd = H.wmap(2, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
+        self.mapb = H.wmap(4, Co, 0, (1, Co, Cop), (1, 1, 1), n_perm=n_perm)
+        dev = self.w.device
+        kf = 2 * _rup(9 * fcip, 64) if self.split else 9 * fcip
+        self.Wf = torch.empty(Cop, kf, device=dev, dtype=torch.float16 if self.x3 else
+                              (torch.bfloat16 if self.split else eng.tdt))
+        self.narrow = bool(narrow)
+        if self.narrow:   # the narrow kernels' forward form (their backward reads the fp32 master weight)
+            self.mapn = H.wmap(15, Co, Ci, (1, Co, 16), (1, Ci, Cip))
+            self.Wn = torch.empty(16, 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
+        if self.x3:   # fp16 pairs of the dgrad form (pack kind 18)
+            self.mapd = H.wmap(18, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
+            self.Wd = torch.empty(Cip, 2 * _rup(9 * Cop, 64), device=dev, dtype=torch.float16) if need_dgrad else None
+        else:
+            self.Wd = torch.empty(Cip, 9 * Cop, device=dev, dtype=eng.tdt) if need_dgrad else None
+        self.bp = torch.empty(Cop, device=dev)
+        self.wr = bool(wr) and Cop == 192 and Cip == 192 and self.split
+        # wr_pair: an upsampling conv (64 -> 256, sub-pixel-major rows) reading a [hi | lo] pair image
+        self.wr_pair = bool(wr) and not self.wr and tied_in and Cip == 64 and fcip == 128 and Cop == 256 and self.split
+        if self.wr_pair:   # + its input-gradient form (kind 16, rows = the 64 input channels)
+            self.mapp = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
+            self.Wp15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
+            self.mapp16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
+            self.Wp16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
+        # wr_n64: conv_before_upsample (192 -> 64) on kair_conv3x3_wr's N <= 64 form
+        self.wr_n64 = (bool(wr) and not self.wr and not self.wr_pair and Cop == 64 and Cip == 192 and self.split and
+                       not tied_in and not self.x3)
+        if self.wr_n64:
+            self.mapc = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wc15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
+            self.mapc16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wc16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
+        if self.wr and self.x3:   # fp16 pairs of w 2^KAIR_X3_WEXP in fragment order (same element counts)
+            self.map15 = H.wmap(22, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.float16)
+            self.map16 = H.wmap(23, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wd16 = torch.empty(Cip * 2 * 9 * Cop, device=dev, dtype=torch.float16)
+        elif self.wr:
+            self.map15 = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
+            self.map16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wd16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
+
+    def fwd(self):
+        """The forward GEMM's B operand."""
+        return H.rows(self.Wf, w_split=self.split)
+
+    def pack_jobs(self):
+        w, b = self.w.detach(), self.b.detach()
+        jobs = [(w, self.Wf, self.mapf), (b, self.bp, self.mapb)]
+        if self.Wd is not None:
+            jobs.append((w, self.Wd, self.mapd))
+        if self.narrow:
+            jobs.append((w, self.Wn, self.mapn))
+        if self.wr:
+            jobs += [(w, self.Wf15, self.map15), (w, self.Wd16, self.map16)]
+        if self.wr_pair:
+            jobs += [(w, self.Wp15, self.mapp), (w, self.Wp16, self.mapp16)]
+        if self.wr_n64:
+            jobs += [(w, self.Wc15, self.mapc), (w, self.Wc16, self.mapc16)]
+        return jobs
+
+
+class EngineBase:
+    COMPUTE_DTYPES = ()      # the compute dtypes the engine implements, of "bf16", "fp32", "fp32x3"
+    X3_AEXP = 4              # fp32x3 activation exponent (default; per engine: self.X3_AEXP, lowered by x3_backoff)
+    X3_BACKOFF_STEP = 6      # exponent drop per range-guard event (x 1/64)
+    X3_BACKOFF_MAX = 4       # events before the guard gives up and raises
+
+    def __init__(self, net, compute_dtype):
+        """No device work: the subclass sets `device`, `cd` (its kernels' compute enum) and its layer objects."""
+        if compute_dtype not in self.COMPUTE_DTYPES:
+            raise ValueError(f"{type(self).__name__}: compute_dtype {compute_dtype!r} (implemented: {self.COMPUTE_DTYPES})")
+        self.net_ref = weakref.ref(net)
+        # fp32x3: the fp32 reference's arithmetic on the 16-bit matrix cores -- every contraction multiplies
+        # fp16 pairs of power-of-2-scaled operands (hi.hi + hi.lo + lo.hi, fp32 accumulation; ~2^-21 relative
+        # per product), activations and gradients fp32 in HBM.  Exponents put the bulk of every operand at
+        # 2^2 .. 2^10 -- the lo half (2^-11 of the value) then stays a normal fp16 number (>= 2^-14) while the
+        # largest values keep >= 16x headroom below fp16's 65504: weights KAIR_X3_WEXP (packs: |w| ~ 0.02 -> ~2^6),
+        # activations X3_AEXP (O(1) -> 2^4), gradients P["e_g"] (the loss normalisation, _x3_grad_exp)
+        self.x3 = compute_dtype == "fp32x3"
+        self.tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        # x3 exponents of the activation class and of the gradient class (offset over the loss normalisation);
+        # lowered by x3_backoff() when the range guard sees an operand leave fp16's window
+        self.X3_AEXP = type(self).X3_AEXP
+        self.x3_gexp_off = 4
+        self.x3_backoffs = 0
+        self._ax = self.X3_AEXP   # the exponent of the GEMM A operands / fp16 outputs of the phase being issued
+        self.plans = PlanPool(self._build_plan)
+        self.plan_mode = "primary"
+        self._packed_version = None
+        self._pack_table = None
+        self.blocks = []          # the blocks with stochastic depth (drop_path_scales); none in the conv nets
+        self.seg_hook = None      # called between the gradient segments of backward() (grad_segments())
+        # repack_always: an engine whose parameters are updated outside torch (the fused trainer's Adam
+        # kernel writes the flat parameter buffer; versions do not move) and that no step graph repacks
+        # -- the eval-mode twin (SwinIR.eval_engine)
+        self.repack_always = False
+
+    def convs(self):
+        """The layer objects whose pack_jobs() make up the weight packs."""
+        raise NotImplementedError
+
+    def _build_plan(self, key, infer):
+        raise NotImplementedError
+
+    def plan(self, *key):
+        return self.plans.get(key, self.plan_mode)
+
+    def pack_jobs(self):
+        return [j for c in self.convs() for j in c.pack_jobs()]
+
+    def pack(self, force=False):
+        """Refresh the packed weight forms (one batched launch) when a parameter's version moved."""
+        net = self.net_ref()
+        ver = None if force or self.repack_always else tuple(p._version for p in net.parameters())
+        if ver is not None and ver == self._packed_version:
+            return
+        ptrs = tuple(p.data_ptr() for p in net.parameters())
+        if self._pack_table is None or self._pack_table[0] != ptrs:   # params re-homed (e.g. flattened)
+            self._pack_table = (ptrs, H.PackTable(self.pack_jobs()))
+        self._pack_table[1].run()
+        self._packed_version = ver
+
+    def _e(self, *shape, dt=torch.float32):
+        return torch.empty(*shape, device=self.device, dtype=dt)
+
+    def _segment_done(self):
+        if self.seg_hook is not None:
+            self.seg_hook()
+
+    # ---- fp32x3 exponents and the range guard's reaction --------------------------------------
+    def _x3_grad_exp(self, numel, weight=1.0):
+        """The fp32x3 gradient exponent: the mean-loss gradient is O(weight / numel) per output element (weight: the
+        loss weight over img_range), so data gradients times 2^(log2(numel / weight) + 4) sit near 2^4 at the loss,
+        2^12 below fp16's overflow."""
+        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
+
+    @staticmethod
+    def x3_upstream_grad_exp(mx):
+        """The gradient exponent for an arbitrary upstream gradient of largest magnitude mx: max -> <= 2^8."""
+        return 8 - int(math.ceil(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 0
+
+    def x3_backoff(self, step=None, act=True, grad=True):
+        """Range guard reaction (kair_range_check saw an inf / NaN the split operands can cause): lower the activation
+        exponent (act: a forward overflow, the loss went non-finite) and / or the gradient exponent (grad: a backward
+        overflow) by `step` (default X3_BACKOFF_STEP), so that operand class gains that much headroom below fp16's
+        65504 (the lo halves of its smallest values go subnormal first: an absolute error <= 2^-25 of the scaled
+        unit).  The caller re-runs the step (re-captured graph).  Raises after X3_BACKOFF_MAX events: the data is not
+        finite in fp32 either, or a weight left its pack window."""
+        if not self.x3:
+            raise RuntimeError("x3_backoff: not an fp32x3 engine")
+        if self.x3_backoffs >= self.X3_BACKOFF_MAX:
+            raise RuntimeError(f"fp32x3 range guard: the step is still non-finite after {self.x3_backoffs} exponent "
+                               f"back-offs (activation 2^{self.X3_AEXP}, gradient offset 2^{self.x3_gexp_off}): the data "
+                               f"is not finite, or a weight left its pack window |w| < 2^{16 - H.X3_WEXP}")
+        step = self.X3_BACKOFF_STEP if step is None else int(step)
+        if act:
+            self.X3_AEXP -= step
+        if grad:
+            self.x3_gexp_off -= step
+        self.x3_backoffs += 1
+        return self.X3_AEXP, self.x3_gexp_off
+
+
+class ConvEngineBase(EngineBase):
+    """Shared plumbing of the conv-net step programs: GEMM launch in the engine's arithmetic, conv weight-gradient
+    helpers.  fp32x3: cd stays F32 for the fp32-rows bookkeeping (gate_cast), the launches go through _nt /
+    conv_wgrad with compute KAIR_COMPUTE_X3."""
+
+    def __init__(self, net, compute_dtype):
+        super().__init__(net, compute_dtype)
+        self.cd = H.BF16 if compute_dtype == "bf16" else H.F32
+
+    def _nt(self, A, B, E, M, N, K):
+        """kair_gemm_nt in the engine's arithmetic; fp32x3: A carries the phase exponent, B the weight packs'."""
+        if self.x3:
+            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
+            H.gemm_nt(A, B, E, M, N, K, H.X3)
+        else:
+            H.gemm_nt(A, B, E, M, N, K, self.cd)
+
+    def conv_wgrad(self, P, c, dz, ld_dz, src_op, M, grads, bias_src=None, ld_bias=None):
+        """weight + bias gradient of conv c: dz [M, Cop] rows (compute dtype), src_op its im2col input;
+        bias_src: the fp32 rows dz was cast from (bias gradient summed before rounding)."""
+        K = 9 * c.Cip
+        S = H.wgrad_splits(M, c.Cop, K)
+        A = H.rows(dz, ld=ld_dz)
+        if self.x3:   # (gradient, activation) operands
+            A.x3_exp, src_op.x3_exp = P["e_g"], self.X3_AEXP
+        H.gemm_tn(A, src_op, P["wg_ws"], S, M, c.Cop, K, H.X3 if self.x3 else self.cd)
+        H.wgrad_finalize(P["wg_ws"], S, c.map, grads[c.w])
+        if bias_src is None:
+            bias_src, ld_bias = dz, ld_dz
+        H.colsum(H.rows(bias_src, ld=ld_bias), M, c.Cop, c.mapb, grads[c.b], P["colsum_ws"])
+
+    def gate_cast(self, P, G, ldg, X, ldx, out, ldo, M, C, kind, slope=0.0, scale=1.0):
+        """out (compute dtype) = scale * G * act'(X).  Returns the fp32 rows to take the bias gradient
+        from: `out` itself in fp32 mode, else an fp32 scratch holding the values before rounding."""
+        if self.cd == H.F32:
+            H.act_grad_cast(G, ldg, X, ldx, out, ldo, M, C, kind, slope, scale)
+            return out, ldo
+        f = P["dzf"].view(-1)[:M * C].view(M, C)
+        H.act_grad_cast(G, ldg, X, ldx, f, C, M, C, kind, slope, scale)
+        H.row_copy(f, C, M, C, H.copy_desc(out, ld=ldo))
+        return f, C
+
+    def wgrad_ws_size(self, shapes):
+        return max(H.wgrad_splits(m, n, k) * n * k for m, n, k in shapes)
+
+
+def drop_path_scales(engine, B, device, generator=None):
+    """Per-block, per-branch stochastic-depth scales (timm DropPath semantics: keep-mask / keep)."""
+    keep = getattr(engine, "_keep", None)
+    if keep is None or keep.device != torch.device(device):   # built once, outside any graph capture
+        rates = torch.tensor([b.dp for b in engine.blocks], dtype=torch.float32)
+        keep = engine._keep = (1.0 - rates).view(-1, 1, 1).to(device)
+    u = torch.rand(len(engine.blocks), 2, B, device=device, generator=generator)
+    return (u < keep).float() / keep
+
+
+def lease_grads(ctx, gE):
+    """First step of an engine Function's backward: check that the node still holds its plan, make it the engine's
+    current one, and carve one flat fp32 buffer into per-parameter gradient views -> (flat, {param: view})."""
+    if ctx.lease is None or ctx.lease.plan is None:
+        raise RuntimeError("kair_amd: backward through a forward whose activations were released "
+                           "(a second backward needs retain_graph-style reuse, which is not supported)")
+    flat = torch.empty(sum(p.numel() for p in ctx.params), device=gE.device)
+    grads, off = {}, 0
+    for p in ctx.params:
+        grads[p] = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    ctx.engine.cur = ctx.lease.plan
+    return flat, grads
+
+
+class ConvNetFunction(torch.autograd.Function):
+    """A whole conv network (RRDBNet / DnCNN / ...) as one autograd node on its step program; the
+    node leases its plan from forward to backward (kair_amd/engine/plans.py)."""
+
+    @classmethod
+    def run(cls, engine, x, params):
+        return cls.apply(engine, autograd_mode(params), x, *params)
+
+    @staticmethod
+    def forward(ctx, engine, mode, x, *params):
+        with plan_mode(engine, mode):
+            E = engine.forward(x.float().contiguous())
+        ctx.engine, ctx.params = engine, params
+        ctx.lease = Lease(engine.cur) if mode == "lease" else None
+        return E.clone()
+
+    @staticmethod
+    def backward(ctx, gE):
+        _, grads = lease_grads(ctx, gE)
+        ctx.engine.backward_from_grad(gE.float(), grads)
+        ctx.lease.release()
+        return (None, None, None) + tuple(grads[p] for p in ctx.params)

@@ -14,15 +14,12 @@ import torch
 import torch.nn as nn
 
 from .. import _hip as H
-from .rrdbnet_engine import ConvEngineBase
-from .swinir_engine import _Conv
-
-
-def _rup(x, m):
-    return (x + m - 1) // m * m
+from .base import ConvEngineBase, _Conv, _rup
 
 
 class DnCNNEngine(ConvEngineBase):
+    COMPUTE_DTYPES = ("bf16", "fp32")   # (its GEMMs are launched in cd directly: no fp32x3 form)
+
     def __init__(self, net, compute_dtype="bf16", residual=True):
         super().__init__(net, compute_dtype)
         self.residual = residual

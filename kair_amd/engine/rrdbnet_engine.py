@@ -13,132 +13,16 @@ gradients of the five convs into one fp32 buffer of the same width (dgrad epilog
 gates them with LeakyReLU' read from the saved post-activation slices, and reduces weight / bias
 gradients with the split-M TN GEMM + deterministic finalize / column sums.
 """
-import math
-import weakref
-
 import torch
 
 from .. import _hip as H
-from .plans import Lease, PlanPool, autograd_mode, plan_mode
-from .swinir_engine import _Conv
-
-
-class ConvEngineBase:
-    """Shared plumbing of the conv-net step programs: packed weights (one batched launch), plan
-    cache, conv forward / weight-gradient helpers."""
-
-    def __init__(self, net, compute_dtype):
-        self.net_ref = weakref.ref(net)
-        if compute_dtype not in ("bf16", "fp32", "fp32x3"):
-            raise ValueError(compute_dtype)
-        # fp32x3 (the reference's fp32 precision class on the 16-bit matrix cores, as SwinIREngine): fp32 activations
-        # and gradients in HBM, every conv product as hi.hi + hi.lo + lo.hi of power-of-2-scaled fp16 pairs (the
-        # split in the GEMM kernels, weights packed as fp16 pairs), fp32 accumulation; cd stays F32 for the
-        # fp32-rows bookkeeping (gate_cast), the launches go through _nt / conv_wgrad with compute KAIR_COMPUTE_X3
-        self.x3 = compute_dtype == "fp32x3"
-        self.cd = H.BF16 if compute_dtype == "bf16" else H.F32
-        self.tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
-        self.X3_AEXP = 4          # activation exponent (lowered by x3_backoff)
-        self.x3_gexp_off = 4      # gradient exponent over the loss normalisation
-        self.x3_backoffs = 0
-        self._ax = self.X3_AEXP   # the exponent of the GEMM A operands of the phase being issued
-        self.plans = PlanPool(self._build_plan)
-        self.plan_mode = "primary"
-        self._packed_version = None
-        self._pack_table = None
-        self.blocks = []          # no stochastic depth in the conv nets (FusedTrainer checks this)
-        self.seg_hook = None      # called between the gradient segments of backward() (grad_segments())
-
-    def _segment_done(self):
-        if self.seg_hook is not None:
-            self.seg_hook()
-
-    X3_BACKOFF_STEP, X3_BACKOFF_MAX = 6, 4
-
-    def _nt(self, A, B, E, M, N, K):
-        """kair_gemm_nt in the engine's arithmetic; fp32x3: A carries the phase exponent, B the weight packs'."""
-        if self.x3:
-            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
-            H.gemm_nt(A, B, E, M, N, K, H.X3)
-        else:
-            H.gemm_nt(A, B, E, M, N, K, self.cd)
-
-    def _x3_grad_exp(self, numel, weight=1.0):
-        """Data gradients of a mean loss are O(weight / numel): times 2^(log2(numel / weight) + 4) they sit near 2^4."""
-        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
-
-    def x3_backoff(self, step=None, act=True, grad=True):
-        """The range guard's reaction (FusedTrainer.check_range; SwinIREngine.x3_backoff)."""
-        if not self.x3:
-            raise RuntimeError("x3_backoff: not an fp32x3 engine")
-        if self.x3_backoffs >= self.X3_BACKOFF_MAX:
-            raise RuntimeError(f"fp32x3 range guard: the step is still non-finite after {self.x3_backoffs} exponent "
-                               f"back-offs: the data is not finite, or a weight left its pack window |w| < "
-                               f"2^{16 - H.X3_WEXP}")
-        step = self.X3_BACKOFF_STEP if step is None else int(step)
-        if act:
-            self.X3_AEXP -= step
-        if grad:
-            self.x3_gexp_off -= step
-        self.x3_backoffs += 1
-        return self.X3_AEXP, self.x3_gexp_off
-
-    def convs(self):
-        raise NotImplementedError
-
-    def plan(self, B, Hh, Ww):
-        return self.plans.get((B, Hh, Ww), self.plan_mode)
-
-    def _build_plan(self, key, infer):
-        raise NotImplementedError
-
-    def pack(self, force=False):
-        net = self.net_ref()
-        ver = None if force else tuple(p._version for p in net.parameters())
-        if ver is not None and ver == self._packed_version:
-            return
-        ptrs = tuple(p.data_ptr() for p in net.parameters())
-        if self._pack_table is None or self._pack_table[0] != ptrs:
-            jobs = [j for c in self.convs() for j in c.pack_jobs()]
-            self._pack_table = (ptrs, H.PackTable(jobs))
-        self._pack_table[1].run()
-        self._packed_version = ver
-
-    def _e(self, *shape, dt=torch.float32):
-        return torch.empty(*shape, device=self.device, dtype=dt)
-
-    def conv_wgrad(self, P, c, dz, ld_dz, src_op, M, grads, bias_src=None, ld_bias=None):
-        """weight + bias gradient of conv c: dz [M, Cop] rows (compute dtype), src_op its im2col input;
-        bias_src: the fp32 rows dz was cast from (bias gradient summed before rounding)."""
-        K = 9 * c.Cip
-        S = H.wgrad_splits(M, c.Cop, K)
-        A = H.rows(dz, ld=ld_dz)
-        if self.x3:   # (gradient, activation) operands
-            A.x3_exp, src_op.x3_exp = P["e_g"], self.X3_AEXP
-        H.gemm_tn(A, src_op, P["wg_ws"], S, M, c.Cop, K, H.X3 if self.x3 else self.cd)
-        H.wgrad_finalize(P["wg_ws"], S, c.map, grads[c.w])
-        if bias_src is None:
-            bias_src, ld_bias = dz, ld_dz
-        H.colsum(H.rows(bias_src, ld=ld_bias), M, c.Cop, c.mapb, grads[c.b], P["colsum_ws"])
-
-    def gate_cast(self, P, G, ldg, X, ldx, out, ldo, M, C, kind, slope=0.0, scale=1.0):
-        """out (compute dtype) = scale * G * act'(X).  Returns the fp32 rows to take the bias gradient
-        from: `out` itself in fp32 mode, else an fp32 scratch holding the values before rounding."""
-        if self.cd == H.F32:
-            H.act_grad_cast(G, ldg, X, ldx, out, ldo, M, C, kind, slope, scale)
-            return out, ldo
-        f = P["dzf"].view(-1)[:M * C].view(M, C)
-        H.act_grad_cast(G, ldg, X, ldx, f, C, M, C, kind, slope, scale)
-        H.row_copy(f, C, M, C, H.copy_desc(out, ld=ldo))
-        return f, C
-
-    def wgrad_ws_size(self, shapes):
-        return max(H.wgrad_splits(m, n, k) * n * k for m, n, k in shapes)
+from .base import ConvEngineBase, _Conv
 
 
 class RRDBNetEngine(ConvEngineBase):
     """Also runs network_rrdb.RRDB (option net_type 'rrdb', basicblock.py:393-428 + upsample_upconv
     455-465): same topology with a configurable activation; see spec_from_rrdb()."""
+    COMPUTE_DTYPES = ("bf16", "fp32", "fp32x3")
 
     def __init__(self, net, compute_dtype="bf16", spec=None):
         super().__init__(net, compute_dtype)
@@ -301,8 +185,7 @@ class RRDBNetEngine(ConvEngineBase):
         HL, WL = P["levels"][-1]
         H.image_to_nhwc(gE.contiguous(), P["dE"], 16, None, 1.0, P["B"], self.out_ch, HL, WL)
         if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            mx = float(gE.abs().max())
-            P["e_g"] = (8 - int(math.ceil(math.log2(mx)))) if mx > 0 and math.isfinite(mx) else 0
+            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()))
         self.backward(grads, P)
 
     def backward(self, grads, P):
@@ -372,35 +255,3 @@ class RRDBNetEngine(ConvEngineBase):
                       9 * gc)
             self.conv_wgrad(P, c, dz, gc, H.im2col(D, Hh, Ww, cin, ld=CD), M, grads, *bs)
         H.axpby_rows(gy, nf, Gd, CD, M, nf, 1.0, 1.0)
-
-
-class ConvNetFunction(torch.autograd.Function):
-    """A whole conv network (RRDBNet / DnCNN / ...) as one autograd node on its step program; the
-    node leases its plan from forward to backward (kair_amd/engine/plans.py)."""
-
-    @classmethod
-    def run(cls, engine, x, params):
-        return cls.apply(engine, autograd_mode(params), x, *params)
-
-    @staticmethod
-    def forward(ctx, engine, mode, x, *params):
-        with plan_mode(engine, mode):
-            E = engine.forward(x.float().contiguous())
-        ctx.engine, ctx.params = engine, params
-        ctx.lease = Lease(engine.cur) if mode == "lease" else None
-        return E.clone()
-
-    @staticmethod
-    def backward(ctx, gE):
-        eng = ctx.engine
-        if ctx.lease is None or ctx.lease.plan is None:
-            raise RuntimeError("kair_amd: backward through a forward whose activations were released")
-        flat = torch.empty(sum(p.numel() for p in ctx.params), device=gE.device)
-        grads, off = {}, 0
-        for p in ctx.params:
-            grads[p] = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        eng.cur = ctx.lease.plan
-        eng.backward_from_grad(gE.float(), grads)
-        ctx.lease.release()
-        return (None, None, None) + tuple(grads[p] for p in ctx.params)

@@ -18,18 +18,14 @@ step can be captured in a HIP graph (kair_amd/engine/trainer.py).
 import contextlib
 import math
 import os
-import weakref
 
 import torch
 
 from .. import _hip as H
-from .plans import Lease, PlanPool, autograd_mode, plan_mode
+from .base import EngineBase, _Conv, _rup, drop_path_scales, lease_grads
+from .plans import Lease, autograd_mode, plan_mode
 
 WINDOW_SIZES = (7, 8)    # the window sides the attention kernels are built for
-
-
-def _rup(x, m):
-    return (x + m - 1) // m * m
 
 
 def swinir_flops(net, Hh, Ww):
@@ -93,7 +89,7 @@ class _Lin:
         dev = self.w.device
         # fp32x3 engine: the rows forms hold fp16 pairs of w 2^KAIR_X3_WEXP interleaved per 64 columns (pack
         # kinds 17 / 19), multiplied hi.hi + hi.lo + lo.hi by kair_gemm_nt (compute KAIR_COMPUTE_X3)
-        self.x3 = getattr(eng, "x3", False)
+        self.x3 = eng.x3
         if self.x3:   # (self.map stays the plain kind-0 map: the weight gradient's finalize layout)
             self.pmap, self.pmapT = H.wmap(17, N, K, n_grp, k_grp), H.wmap(19, N, K, n_grp, k_grp)
             self.Wp = torch.empty(self.Np, 2 * _rup(self.Kp, 64), device=dev, dtype=torch.float16) if rows else None
@@ -124,104 +120,6 @@ class _Lin:
             jobs.append((w, self.Wg, self.mapg))
         if self.Wgt is not None:
             jobs.append((w, self.Wgt, self.mapgt))
-        return jobs
-
-
-class _Conv:
-    """A 3x3 conv's packed forms: forward [Cop][9*Cip] and input-gradient [Cip][9*Cop].
-
-    split (bf16 engines): the forward form holds a hi/lo bf16 pair per weight (pack kind 9,
-    kair_operand.w_split), so the forward product sees the fp32 master weight to ~16 bits.  Plain
-    bf16 weight rounding shifts every output pixel by the same sum(dW * a) and biases PSNR
-    (DESIGN.md "parity at bf16"); activation rounding is unbiased and averages out."""
-
-    def __init__(self, eng, mod, Cop, Cip, need_dgrad=True, split=None, n_perm=0, tied_in=False, fwd_cip=None,
-                 narrow=False, wr=False):
-        """n_perm = r*r: output channels stored sub-pixel-major for a following PixelShuffle(r)
-        (kair_wmap.n_perm; the KAIR_OUT_PSHUF_SPM / PUNSHUF_SPM epilogues store 16 bytes at a time).
-        tied_in: the forward form repeats the input channels in both halves of Cip (kair_wmap kG = 2),
-        for an input held as a hi/lo pair in channels [0, Ci) and [Cip/2, Cip/2 + Ci)
-        (kair_image_to_nhwc_hilo); the weight gradient keeps the plain map (the hi channels).
-        fwd_cip: the forward form's packed input width when it differs from Cip (a [hi | lo] pair image of
-        2 x Cip channels read through tied weights: the SwinIR tail under split_act).
-        narrow: a 64 -> NR <= 4 conv run by the narrow-output kernels (kair_conv3x3_narrow_*): its forward
-        form is pack kind 15 (16x16x32 fragment order, hi/lo halves), the backward reads the fp32 weight.
-        wr: a 192 -> 192 conv also packed for kair_conv3x3_wr: forward pack kind 15, input gradient kind 16
-        (fp32x3: kair_conv3x3_wr_x3's fp16 pairs, kinds 22 / 23)."""
-        self.w, self.b = mod.weight, mod.bias
-        Co, Ci = self.w.shape[:2]
-        self.Co, self.Ci, self.Cop, self.Cip = Co, Ci, Cop, Cip
-        if split is None:
-            split = getattr(eng, "split_conv", False)
-        x3 = getattr(eng, "x3", False)   # (the RRDBNet / USRNet engines share this class and have no x3 form)
-        self.split = (bool(split) and eng.tdt == torch.bfloat16) or x3
-        self.x3 = x3
-        self.n_perm = n_perm
-        self.map = H.wmap(1, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
-        fcip = fwd_cip or Cip
-        self.fcip = fcip
-        kf_grp = (2, Ci, fcip // 2) if tied_in else (1, Ci, Cip)
-        self.mapf = H.wmap(9 if self.split else 1, Co, Ci, (1, Co, Cop), kf_grp, n_perm=n_perm)
-        self.mapd = H.wmap(2, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
-        self.mapb = H.wmap(4, Co, 0, (1, Co, Cop), (1, 1, 1), n_perm=n_perm)
-        dev = self.w.device
-        kf = 2 * _rup(9 * fcip, 64) if self.split else 9 * fcip
-        self.Wf = torch.empty(Cop, kf, device=dev, dtype=torch.float16 if self.x3 else
-                              (torch.bfloat16 if self.split else eng.tdt))
-        self.narrow = bool(narrow)
-        if self.narrow:   # the narrow kernels' forward form (their backward reads the fp32 master weight)
-            self.mapn = H.wmap(15, Co, Ci, (1, Co, 16), (1, Ci, Cip))
-            self.Wn = torch.empty(16, 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
-        if self.x3:   # fp16 pairs of the dgrad form (pack kind 18)
-            self.mapd = H.wmap(18, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
-            self.Wd = torch.empty(Cip, 2 * _rup(9 * Cop, 64), device=dev, dtype=torch.float16) if need_dgrad else None
-        else:
-            self.Wd = torch.empty(Cip, 9 * Cop, device=dev, dtype=eng.tdt) if need_dgrad else None
-        self.bp = torch.empty(Cop, device=dev)
-        self.wr = bool(wr) and Cop == 192 and Cip == 192 and self.split
-        # wr_pair: an upsampling conv (64 -> 256, sub-pixel-major rows) reading a [hi | lo] pair image
-        self.wr_pair = bool(wr) and not self.wr and tied_in and Cip == 64 and fcip == 128 and Cop == 256 and self.split
-        if self.wr_pair:   # + its input-gradient form (kind 16, rows = the 64 input channels)
-            self.mapp = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
-            self.Wp15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
-            self.mapp16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip), n_perm=n_perm)
-            self.Wp16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
-        # wr_n64: conv_before_upsample (192 -> 64) on kair_conv3x3_wr's N <= 64 form
-        self.wr_n64 = (bool(wr) and not self.wr and not self.wr_pair and Cop == 64 and Cip == 192 and self.split and
-                       not tied_in and not self.x3)
-        if self.wr_n64:
-            self.mapc = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wc15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
-            self.mapc16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wc16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
-        if self.wr and self.x3:   # fp16 pairs of w 2^KAIR_X3_WEXP in fragment order (same element counts)
-            self.map15 = H.wmap(22, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.float16)
-            self.map16 = H.wmap(23, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wd16 = torch.empty(Cip * 2 * 9 * Cop, device=dev, dtype=torch.float16)
-        elif self.wr:
-            self.map15 = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
-            self.map16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
-            self.Wd16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
-
-    def fwd(self):
-        """The forward GEMM's B operand."""
-        return H.rows(self.Wf, w_split=self.split)
-
-    def pack_jobs(self):
-        w, b = self.w.detach(), self.b.detach()
-        jobs = [(w, self.Wf, self.mapf), (b, self.bp, self.mapb)]
-        if self.Wd is not None:
-            jobs.append((w, self.Wd, self.mapd))
-        if self.narrow:
-            jobs.append((w, self.Wn, self.mapn))
-        if self.wr:
-            jobs += [(w, self.Wf15, self.map15), (w, self.Wd16, self.map16)]
-        if self.wr_pair:
-            jobs += [(w, self.Wp15, self.mapp), (w, self.Wp16, self.mapp16)]
-        if self.wr_n64:
-            jobs += [(w, self.Wc15, self.mapc), (w, self.Wc16, self.mapc16)]
         return jobs
 
 
@@ -275,7 +173,9 @@ class _Blk:
         return (self.qkv, self.proj, self.fc1, self.fc2)
 
 
-class SwinIREngine:
+class SwinIREngine(EngineBase):
+    COMPUTE_DTYPES = ("bf16", "fp32", "fp32x3")
+
     def __init__(self, net, compute_dtype="bf16", split_conv=True, fused_blocks=True, fused_mlp=None,
                  split_linear=None, fused_mlp_bwd=False, side_stream=True, side_ctas=None, side_priority=0,
                  split_act=True, conv_wr=True, head_pad=None, grouped_wgrad=None):
@@ -290,26 +190,11 @@ class SwinIREngine:
         each (kair_swin_attn_fwd, kair_swin_mlp_fwd) where the geometry allows it (6 heads,
         Cp = 192, hidden padded to 384); fused_mlp (default: fused_blocks) selects the MLP-half
         kernel separately."""
-        self.net_ref = weakref.ref(net)
-        if compute_dtype not in ("bf16", "fp32", "fp32x3"):
-            raise ValueError(compute_dtype)
-        # fp32x3: the fp32 reference's arithmetic on the 16-bit matrix cores -- every contraction multiplies
-        # fp16 pairs of power-of-2-scaled operands (hi.hi + hi.lo + lo.hi, fp32 accumulation; ~2^-21 relative
-        # per product), operands fp32 (split inside the kernels) or fp16 hi/lo planes; the unfused launch
-        # sequence of the fp32 engine.  Exponents put the bulk of every operand at 2^2 .. 2^10 -- the lo half
-        # (2^-11 of the value) then stays a normal fp16 number (>= 2^-14) while the largest values keep
-        # >= 16x headroom below fp16's 65504: weights KAIR_X3_WEXP (packs: |w| ~ 0.02 -> ~2^6),
-        # activations X3_AEXP (O(1) -> 2^4), gradients P["e_g"] (the loss normalisation, _x3_grad_exp)
-        self.x3 = compute_dtype == "fp32x3"
-        self._ax = 0   # x3: the exponent of the GEMM A operands / fp16 outputs of the phase being issued
-        # x3 exponents of the activation class and of the gradient class (offset over the loss normalisation);
-        # lowered together by x3_backoff() when the range guard sees an operand leave fp16's window
-        self.X3_AEXP = 4
-        self.x3_gexp_off = 4
-        self.x3_backoffs = 0
+        super().__init__(net, compute_dtype)
+        # fp32x3 (EngineBase): operands fp32 (split inside the kernels) or fp16 hi/lo planes; the unfused launch
+        # sequence of the fp32 engine
         self.cd = H.BF16 if compute_dtype in ("bf16", "fp32x3") else H.F32
         self.tn_cd = H.X3 if self.x3 else self.cd   # kair_gemm_tn compute of the weight gradients
-        self.tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
         self.split_conv = bool(split_conv) and compute_dtype == "bf16"
         # split activations only pay with split weights (a bf16 weight rounding dominates otherwise), and
         # the tied pair forms need split weight packs
@@ -420,11 +305,6 @@ class SwinIREngine:
         else:
             raise NotImplementedError(self.upsampler)
         self.blocks = [b for blks, _ in self.rstb for b in blks]
-        self.plans = PlanPool(self._build_plan)
-        self.plan_mode = "primary"
-        self._packed_version = None
-        self._pack_table = None
-        self.seg_hook = None   # called between the gradient segments of backward() (grad_segments())
         # Swin-block weight gradients: deferred to the end of each RSTB and issued as ONE grouped
         # launch (kair_wgrad_grouped: 4 linears x depth blocks) where the bf16 TN ring takes the shapes;
         # otherwise one gemm_tn + finalize per linear, issued in place.  Narrow blocks (Cp = 64, SwinIR-lightweight) too:
@@ -493,10 +373,6 @@ class SwinIREngine:
                     list(net.layers[0].parameters()))
         return segs
 
-    def _segment_done(self):
-        if self.seg_hook is not None:
-            self.seg_hook()
-
     # ------------------------------------------------------------------------------------
     def convs(self):
         cs = [self.conv_first] + [c for _, c in self.rstb] + [self.cab]
@@ -510,25 +386,8 @@ class SwinIREngine:
             cs += [self.up1]
         return cs
 
-    def pack(self, force=False):
-        net = self.net_ref()
-        # repack_always: an engine whose parameters are updated outside torch (the fused trainer's Adam
-        # kernel writes the flat parameter buffer; versions do not move) and that no step graph repacks
-        # -- the eval-mode twin (SwinIR.eval_engine)
-        force = force or getattr(self, "repack_always", False)
-        ver = None if force else tuple(p._version for p in net.parameters())
-        if ver is not None and ver == self._packed_version:
-            return
-        ptrs = tuple(p.data_ptr() for p in net.parameters())
-        if self._pack_table is None or self._pack_table[0] != ptrs:   # params re-homed (e.g. flattened)
-            jobs = [j for c in self.convs() for j in c.pack_jobs()]
-            jobs += [j for b in self.blocks for l in b.linears() for j in l.pack_jobs()]
-            self._pack_table = (ptrs, H.PackTable(jobs))
-        self._pack_table[1].run()
-        self._packed_version = ver
-
-    def plan(self, B, Hh, Ww):
-        return self.plans.get((B, Hh, Ww), self.plan_mode)
+    def pack_jobs(self):
+        return super().pack_jobs() + [j for b in self.blocks for l in b.linears() for j in l.pack_jobs()]
 
     def _build_plan(self, key, infer):
         """Buffers of one input shape.  infer=True: forward only -- the Swin blocks ping-pong between
@@ -540,7 +399,7 @@ class SwinIREngine:
         if Hh % self.ws or Ww % self.ws:
             raise ValueError(f"kair_amd SwinIR: the {Hh}x{Ww} token grid is no multiple of window_size {self.ws}")
         nWin = M // self.T
-        e = lambda *s, dt=f32: torch.empty(*s, device=dev, dtype=dt)
+        e = self._e
         hf = torch.float16
         P = {"B": B, "H": Hh, "W": Ww, "M": M, "nWin": nWin}
         # fp32x3: the exponent of the backward's data gradients (the mean loss over the output image)
@@ -862,37 +721,6 @@ class SwinIREngine:
             return
         H.gemm_nt(A, B, E, M, N, K, cd)
 
-    X3_AEXP = 4   # fp32x3 activation exponent (default; per engine: self.X3_AEXP, lowered by x3_backoff)
-    X3_BACKOFF_STEP = 6      # exponent drop per range-guard event (x 1/64)
-    X3_BACKOFF_MAX = 4       # events before the guard gives up and raises
-
-    def _x3_grad_exp(self, numel, weight=1.0):
-        """The fp32x3 gradient exponent: the mean-loss gradient is O(weight / numel) per output element (weight: the
-        loss weight over img_range), so data gradients times 2^(log2(numel / weight) + 4) sit near 2^4 at the loss,
-        2^12 below fp16's overflow."""
-        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
-
-    def x3_backoff(self, step=None, act=True, grad=True):
-        """Range guard reaction (kair_range_check saw an inf / NaN the split operands can cause): lower the activation
-        exponent (act: a forward overflow, the loss went non-finite) and / or the gradient exponent (grad: a backward
-        overflow) by `step` (default X3_BACKOFF_STEP), so that operand class gains that much headroom below fp16's
-        65504 (the lo halves of its smallest values go subnormal first: an absolute error <= 2^-25 of the scaled
-        unit).  The caller re-runs the step (re-captured graph).  Raises after X3_BACKOFF_MAX events: the data is not
-        finite in fp32 either, or a weight left its pack window."""
-        if not self.x3:
-            raise RuntimeError("x3_backoff: not an fp32x3 engine")
-        if self.x3_backoffs >= self.X3_BACKOFF_MAX:
-            raise RuntimeError(f"fp32x3 range guard: the step is still non-finite after {self.x3_backoffs} exponent "
-                               f"back-offs (activation 2^{self.X3_AEXP}, gradient offset 2^{self.x3_gexp_off}): the data "
-                               f"is not finite, or a weight left its pack window |w| < 2^{16 - H.X3_WEXP}")
-        step = self.X3_BACKOFF_STEP if step is None else int(step)
-        if act:
-            self.X3_AEXP -= step
-        if grad:
-            self.x3_gexp_off -= step
-        self.x3_backoffs += 1
-        return self.X3_AEXP, self.x3_gexp_off
-
     def _forward_tail(self, P):
         """Reconstruction tail: P['fb'] (conv_after_body + residual) -> P['E']."""
         cd, Cp, M, B, Hh, Ww = self.cd, self.Cp, P["M"], P["B"], P["H"], P["W"]
@@ -1090,8 +918,7 @@ class SwinIREngine:
         # so scatter with the image->nhwc kernel (channel stride / pre-shuffle layout).
         inv = 1.0 / self.img_range   # E = v / img_range + ...
         if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            mx = float(gE.abs().max()) * inv
-            P["e_g"] = (8 - int(math.ceil(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 0) + e_off   # max -> <= 2^8
+            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()) * inv) + e_off
         if self.upsampler != "pixelshuffledirect":
             H.image_to_nhwc(gE.contiguous(), P["dE"], P.get("dE_ld", 16), None, inv, B, self.in_ch, Hh * self.scale,
                             Ww * self.scale)
@@ -1488,16 +1315,8 @@ class SwinIRFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gE):
         eng = ctx.engine
-        if ctx.lease is None or ctx.lease.plan is None:
-            raise RuntimeError("kair_amd SwinIR: backward through a forward whose activations were released "
-                               "(a second backward needs retain_graph-style reuse, which is not supported)")
-        flat = torch.empty(sum(p.numel() for p in ctx.params), device=gE.device)
-        grads, off = {}, 0
-        for p in ctx.params:
-            grads[p] = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        P = ctx.lease.plan
-        eng.cur = P
+        flat, grads = lease_grads(ctx, gE)
+        P = eng.cur
         full = gE
         if gE.shape[-2:] != P["E"].shape[-2:]:
             full = torch.zeros_like(P["E"])
@@ -1514,13 +1333,3 @@ class SwinIRFunction(torch.autograd.Function):
                 eng.backward_from_grad(full.float(), grads, e_off=e_off)
         ctx.lease.release()
         return (None, None, None) + tuple(grads[p] for p in ctx.params)
-
-
-def drop_path_scales(engine, B, device, generator=None):
-    """Per-block, per-branch stochastic-depth scales (timm DropPath semantics: keep-mask / keep)."""
-    keep = getattr(engine, "_keep", None)
-    if keep is None or keep.device != torch.device(device):   # built once, outside any graph capture
-        rates = torch.tensor([b.dp for b in engine.blocks], dtype=torch.float32)
-        keep = engine._keep = (1.0 - rates).view(-1, 1, 1).to(device)
-    u = torch.rand(len(engine.blocks), 2, B, device=device, generator=generator)
-    return (u < keep).float() / keep

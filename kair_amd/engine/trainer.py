@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _hip as H
+from .base import drop_path_scales
 from .comm import allreduce_mean_, allreduce_sum_, broadcast_params_
 
 
@@ -107,7 +108,7 @@ class FusedTrainer:
         # the flat gradients / parameters (+ the loss on one GPU) into a device flag that the Adam kernel reads (a
         # flagged step updates nothing); the host reads the flag one step later (pinned copy + event), lowers the
         # engine's exponents (x3_backoff) and re-runs the flagged step on its own batch before going on.
-        self.range_guard = bool(getattr(self.engine, "x3", False))
+        self.range_guard = self.engine.x3
         self.range_events = []   # (step, flag bits, (activation exp, gradient exp offset) after the back-off)
         if self.range_guard:
             self.rflag = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -119,7 +120,6 @@ class FusedTrainer:
             # activation / gradient back-off cannot cure it, so the guard raises after X3_BACKOFF_MAX re-runs)
             self.p_limit = 3.0e38
         if any(b.dp > 0 for b in self.engine.blocks):
-            from .swinir_engine import drop_path_scales
             drop_path_scales(self.engine, 1, self.device)   # materialise the keep-prob table eagerly
 
     # ------------------------------------------------------------------------------------
@@ -132,8 +132,7 @@ class FusedTrainer:
         eng = self.engine
         drop = None
         if any(b.dp > 0 for b in eng.blocks) and self.net.training:
-            from .swinir_engine import drop_path_scales
-            drop = drop_path_scales(eng, L.shape[0], L.device)
+            drop =drop_path_scales(eng, L.shape[0], L.device)
         eng._packed_version = None           # weights change every step: always repack
         if cond:
             eng.forward(L, *cond)

@@ -26,14 +26,12 @@ the replicate-padded grid (v1:148-151) and crops its output (v1:164) -- kair_usr
 (crop adjoint) of the output gradient and the fold (replicate adjoint) of the input gradient in
 backward.  B*Hp*Wp < 2^24.
 """
-import math
-import weakref
-
 import torch
 import torch.nn as nn
 
 from .. import _hip as H
-from .plans import Lease, PlanPool, autograd_mode, plan_mode
+from .base import ConvEngineBase, lease_grads
+from .plans import Lease, autograd_mode, plan_mode
 
 C8 = 8   # channel stride of the ResUNet input (x, beta) and of the tail-output gradient rows
 
@@ -47,7 +45,15 @@ def _mods(m):
     return list(m) if isinstance(m, nn.Sequential) else [m]
 
 
-class _Conv3:
+class _Packs:
+    """A bias-free conv's two packs of its weight `w`: Wf / mapf (forward) and Wd / mapd (input gradient)."""
+
+    def pack_jobs(self):
+        w = self.w.detach()
+        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
+
+
+class _Conv3(_Packs):
     """Bias-free 3x3 conv: forward [Cop][9 Cip] (kind 1) and input-gradient [Cip][9 Cop] (kind 2) packs."""
 
     def __init__(self, eng, mod, Cop=None, Cip=None):
@@ -65,12 +71,8 @@ class _Conv3:
             self.Wf = eng._e(self.Cop, 9 * self.Cip, dt=eng.tdt)
             self.Wd = eng._e(self.Cip, 9 * self.Cop, dt=eng.tdt)
 
-    def pack_jobs(self):
-        w = self.w.detach()
-        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
 
-
-class _Down:
+class _Down(_Packs):
     """Conv2d(Ci, Co, 2, stride 2, bias=False) (basicblock.downsample_strideconv, basicblock.py:495-501):
     forward through the space-to-depth operand with the [Co][4 Ci] pack (kind 7); input gradient as a
     1x1 GEMM into a pixel-shuffle store with the [4 Ci][Co] pack (kind 8); weight gradient kind 7.
@@ -89,12 +91,8 @@ class _Down:
             self.Wf = eng._e(self.Co, 4 * self.Ci, dt=eng.tdt)
             self.Wd = eng._e(4 * self.Ci, self.Co, dt=eng.tdt)
 
-    def pack_jobs(self):
-        w = self.w.detach()
-        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
 
-
-class _Up:
+class _Up(_Packs):
     """ConvTranspose2d(Ci, Co, 2, stride 2, bias=False) (basicblock.upsample_convtranspose,
     basicblock.py:471-477), weight [Ci][Co][2][2]: forward as a 1x1 GEMM into a pixel-shuffle store
     with the [4 Co][Ci] pack (kind 8 over (Ci, Co)); input gradient through the space-to-depth operand
@@ -114,32 +112,20 @@ class _Up:
             self.Wf = eng._e(4 * self.Co, self.Ci, dt=eng.tdt)
             self.Wd = eng._e(self.Ci, 4 * self.Co, dt=eng.tdt)
 
-    def pack_jobs(self):
-        w = self.w.detach()
-        return [(w, self.Wf, self.mapf), (w, self.Wd, self.mapd)]
-
 
 class _RB:
     def __init__(self, eng, rb):
         self.c1, self.c2 = _Conv3(eng, rb.res[0]), _Conv3(eng, rb.res[2])
 
 
-class USRNetEngine:
+class USRNetEngine(ConvEngineBase):
+    COMPUTE_DTYPES = ("bf16", "fp32", "fp32x3")
+
     def __init__(self, net, compute_dtype="bf16"):
-        self.net_ref = weakref.ref(net)
-        if compute_dtype not in ("bf16", "fp32", "fp32x3"):
-            raise ValueError(compute_dtype)
-        # fp32x3 (the reference's fp32 precision class on the 16-bit matrix cores, as RRDBNetEngine): fp32 maps and
-        # gradients in HBM, every ResUNet product as hi.hi + hi.lo + lo.hi of power-of-2-scaled fp16 pairs (split in
-        # the GEMM kernels, weights packed as fp16 pairs), fp32 accumulation; the FFT / DataNet / HyPaNet passes are
-        # the fp32 engine's.  cd stays F32, the launches go through _nt / _wgrad with compute KAIR_COMPUTE_X3
-        self.x3 = compute_dtype == "fp32x3"
-        self.cd = H.BF16 if compute_dtype == "bf16" else H.F32
-        self.tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
-        self.X3_AEXP = 4          # activation exponent (lowered by x3_backoff)
-        self.x3_gexp_off = 4      # gradient exponent over the loss normalisation
-        self.x3_backoffs = 0
-        self._ax = self.X3_AEXP   # the exponent of the GEMM A operands of the phase being issued
+        # fp32x3 (EngineBase): the ResUNet products in the split-fp16 arithmetic (split in the GEMM kernels, weights
+        # packed as fp16 pairs, the launches through _nt / _wgrad); the FFT / DataNet / HyPaNet passes are the fp32
+        # engine's
+        super().__init__(net, compute_dtype)
         p = net.p
         self.device = p.m_head.weight.device
         self.n = net.n
@@ -166,44 +152,6 @@ class USRNetEngine:
         self.nc = [self.head.Co] + [d.Co for d in self.downs]
         if any(c % 8 for c in self.nc):
             raise NotImplementedError("kair_amd USRNet: ResUNet channel counts must be multiples of 8")
-        self.plans = PlanPool(self._build_plan)
-        self.plan_mode = "primary"
-        self._packed_version = None
-        self._pack_table = None
-        self.blocks = []
-
-    def _e(self, *shape, dt=torch.float32):
-        return torch.empty(*shape, device=self.device, dtype=dt)
-
-    X3_BACKOFF_STEP, X3_BACKOFF_MAX = 6, 4
-
-    def _nt(self, A, B, E, M, N, K):
-        """kair_gemm_nt in the engine's arithmetic; fp32x3: A carries the phase exponent, B the weight packs'."""
-        if self.x3:
-            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
-            H.gemm_nt(A, B, E, M, N, K, H.X3)
-        else:
-            H.gemm_nt(A, B, E, M, N, K, self.cd)
-
-    def _x3_grad_exp(self, numel, weight=1.0):
-        """Data gradients of a mean loss are O(weight / numel): times 2^(log2(numel / weight) + 4) they sit near 2^4."""
-        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
-
-    def x3_backoff(self, step=None, act=True, grad=True):
-        """The range guard's reaction (FusedTrainer.check_range; RRDBNetEngine.x3_backoff)."""
-        if not self.x3:
-            raise RuntimeError("x3_backoff: not an fp32x3 engine")
-        if self.x3_backoffs >= self.X3_BACKOFF_MAX:
-            raise RuntimeError(f"fp32x3 range guard: the step is still non-finite after {self.x3_backoffs} exponent "
-                               f"back-offs: the data is not finite, or a weight left its pack window |w| < "
-                               f"2^{16 - H.X3_WEXP}")
-        step = self.X3_BACKOFF_STEP if step is None else int(step)
-        if act:
-            self.X3_AEXP -= step
-        if grad:
-            self.x3_gexp_off -= step
-        self.x3_backoffs += 1
-        return self.X3_AEXP, self.x3_gexp_off
 
     def convs(self):
         cs = [self.head, self.tail] + self.downs + self.ups
@@ -212,27 +160,12 @@ class USRNetEngine:
                 cs += [rb.c1, rb.c2]
         return cs
 
-    def pack(self, force=False):
-        net = self.net_ref()
-        ver = None if force else tuple(p._version for p in net.parameters())
-        if ver is not None and ver == self._packed_version:
-            return
-        ptrs = tuple(p.data_ptr() for p in net.parameters())
-        if self._pack_table is None or self._pack_table[0] != ptrs:
-            jobs = [j for c in self.convs() for j in c.pack_jobs()]
-            self._pack_table = (ptrs, H.PackTable(jobs))
-        self._pack_table[1].run()
-        self._packed_version = ver
-
     def _hyp(self):
         return [t for m in self.hyp for t in (m.weight, m.bias)]
 
     # ------------------------------------------------------------------------------------
     def _chain(self, M, c, n):
         return [{"h": self._e(M, c, dt=self.tdt), "out": self._e(M, c)} for _ in range(n)]
-
-    def plan(self, B, h, w, sf, kh, kw):
-        return self.plans.get((B, h, w, sf, kh, kw), self.plan_mode)
 
     def _build_plan(self, key, infer):
         B, h, w, sf, kh, kw = key
@@ -274,7 +207,7 @@ class USRNetEngine:
         shapes = [(M[0], nc[0], 9 * C8), (M[0], C8, 9 * nc[0])]
         shapes += [(M[l], nc[l], 9 * nc[l]) for l in range(4)]
         shapes += [(M[l + 1], nc[l + 1], 4 * nc[l]) for l in range(3)]
-        P["wg_ws"] = e(max(H.wgrad_splits(m, n, k) * n * k for m, n, k in shapes))
+        P["wg_ws"] = e(self.wgrad_ws_size(shapes))
         return P
 
     # ------------------------------------------------------------------------------------
@@ -384,8 +317,7 @@ class USRNetEngine:
         P = self.cur
         H.image_to_nhwc(gE.contiguous(), P["gE"], C8, None, 1.0, P["B"], self.out_nc, P["H"], P["W"])
         if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            mx = float(gE.abs().max())
-            P["e_g"] = (8 - int(math.ceil(math.log2(mx)))) if mx > 0 and math.isfinite(mx) else 0
+            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()))
         self.backward(grads, P)
 
     def backward(self, grads, P):
@@ -501,15 +433,7 @@ class USRNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gE):
-        eng = ctx.engine
-        if ctx.lease is None or ctx.lease.plan is None:
-            raise RuntimeError("kair_amd USRNet: backward through a forward whose activations were released")
-        flat = torch.empty(sum(p.numel() for p in ctx.params), device=gE.device)
-        grads, off = {}, 0
-        for p in ctx.params:
-            grads[p] = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        eng.cur = ctx.lease.plan
-        eng.backward_from_grad(gE.float(), grads)
+        _, grads = lease_grads(ctx, gE)
+        ctx.engine.backward_from_grad(gE.float(), grads)
         ctx.lease.release()
         return (None,) * 6 + tuple(grads[p] for p in ctx.params)

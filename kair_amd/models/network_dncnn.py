@@ -13,8 +13,8 @@ substitute for a device call.
 import torch
 import torch.nn as nn
 
+from ..engine.base import ConvNetFunction
 from ..engine.dncnn_engine import DnCNNEngine
-from ..engine.rrdbnet_engine import ConvNetFunction
 
 
 def _act(a, slope=0.2):

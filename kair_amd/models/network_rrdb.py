@@ -11,7 +11,8 @@ import math
 
 import torch.nn as nn
 
-from ..engine.rrdbnet_engine import ConvNetFunction, RRDBNetEngine
+from ..engine.base import ConvNetFunction
+from ..engine.rrdbnet_engine import RRDBNetEngine
 
 
 def _act(a, slope=0.2):

@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 import torch.nn.init as init
 
-from ..engine.rrdbnet_engine import RRDBNetEngine, ConvNetFunction
+from ..engine.base import ConvNetFunction
+from ..engine.rrdbnet_engine import RRDBNetEngine
 
 
 def initialize_weights(net_l, scale=1):
