@@ -770,6 +770,50 @@ int kair_rgb2gray8(const float* x, int N, int H, int W, int mode, float* out, vo
 int kair_synth_jpeg(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int B, int PS,
                     int is_color, float* outH, float* outL, void* stream);
 
+/* ---- blind-SR (BSRGAN) training data (csrc/synth_blindsr.hip; utils/utils_blindsr.py is the host statement) --------
+ * A batch lives in a padded fp32 buffer [B][3][Hmax][Wmax]; sample b uses the top-left (h, w) corner.  The program
+ * table holds, per sample and slot, a row of 16 ints {op, h_in, w_in, h_out, w_out, i0, i1, quality, 8 x float32 bits}:
+ * op 0 copy; 1 blur (i0 ksize; floats lambda_1, lambda_2, theta); 2 resize (i0 kind: 1 bilinear, 2 bicubic a = -0.75,
+ * 3 area, 4 MATLAB bicubic x1/2); 3 blur + decimate (i0 ksize, i1 sf_w: [0::sf_w, 0::sf_w] of the blur with the
+ * kernel centre moved by (sf_w - 1) / 2); 4 noise (i0 mode: 0 per channel, 1 gray, 2 correlated; floats sigma, then
+ * the lower factor L00 L10 L11 L20 L21 L22); 5 JPEG (a copy in kair_bsr_ops; `quality` is what
+ * kair_jpeg_roundtrip_var reads, 0 on every other row).  Sizes read from the table are clamped into the buffer.
+ *
+ * kair_bsr_crop: dst [B][3][PS][PS] = the augmented PS^2 crops; head[b * hstride + {0..5}] = {image, rnd_h, rnd_w,
+ * mode, lq_h, lq_w}.  kair_bsr_finish: outL [B][3][lq][lq] = src[b][:, lq_h : lq_h + lq, lq_w : lq_w + lq] of the
+ * [B][3][PS][PS] buffer, outH [B][3][lq sf][lq sf] = the augmented crop at (lq_h sf, lq_w sf).  C must be 3.
+ *
+ * kair_bsr_kernels: out[(s * B + b) * kstride + ...] = the ksize^2 Gaussian kernel of row (b, s) for every blur and
+ * blur + decimate row, table[b * tstride + s * slot_stride + ...], s < nslot (fp64 formula of kair_usr_gauss_kernels;
+ * ksize clamped to ksize^2 <= kstride).
+ *
+ * kair_bsr_ops: one slot, src -> dst (two different buffers), rows at table[b * tstride], kernels k[b * kstride].
+ * Blur: sum_{u, v} k[u][v] in[mirror(i + ks/2 - u)][mirror(j + ks/2 - v)], the reflection that does not repeat the
+ * edge sample (scipy.ndimage.convolve mode='mirror'), one fp32 fmaf chain in (u, v) order; ks <= 25 runs from an LDS
+ * tile, a larger ks (or direct != 0, for tests) on the one-thread-per-output loop with the same bits.  Resize: half-pixel
+ * centres, replicate borders, coordinates in fp64; area is the exact mean over the footprint [i h_in / h_out,
+ * (i + 1) h_in / h_out); kind 4 reads the caller's taps (utils_image.bicubic_taps(n, ceil(n / 2), 0.5): indices
+ * [n_out][P] and weights) made for a (taps_h_in, taps_w_in) image, and a row of another size takes area instead.
+ * Noise: Philox normals (kair_synth_dn's) keyed by (seed, 8 step + slot) and the buffer element index.  Every output
+ * but a copy is clipped to [0, 1]; pixels outside (h_out, w_out) are not written.
+ *
+ * kair_jpeg_roundtrip_var (csrc/synth_jpeg.hip): the colour round trip of kair_jpeg_roundtrip for sample n's corner
+ * (hw[n * hwstride], hw[n * hwstride + 1]) of x [N][3][Hmax][Wmax], at quality[n * qstride]; quality <= 0 copies;
+ * pixels outside the corner are not written; out may be x.  w_min: the caller's lower bound on the widths, >= 5 (below
+ * it libjpeg uses another upsampler: an argument error).  workspace: kair_jpeg_workspace_bytes(N, 3, Hmax, Wmax). */
+int kair_bsr_crop(const float* pool, int N, int C, int Hs, int Ws, const int* head, int hstride, int B, int PS,
+                  float* dst, void* stream);
+int kair_bsr_finish(const float* pool, int N, int C, int Hs, int Ws, const int* head, int hstride, int B, int PS, int sf,
+                    int lq, const float* src, float* outL, float* outH, void* stream);
+int kair_bsr_kernels(const int* table, int tstride, int slot_stride, int nslot, int B, float* out, long kstride,
+                     void* stream);
+int kair_bsr_ops(const float* src, float* dst, int B, int Hmax, int Wmax, const int* table, int tstride, const float* k,
+                 long kstride, const int* taps_ih, const float* taps_wh, const int* taps_iw, const float* taps_ww, int P,
+                 int taps_h_in, int taps_w_in, unsigned long long seed, unsigned long long step, int slot, int direct,
+                 void* stream);
+int kair_jpeg_roundtrip_var(const float* x, int N, int Hmax, int Wmax, const int* hw, int hwstride, int w_min,
+                            const int* quality, int qstride, float* out, void* workspace, void* stream);
+
 const char* kair_last_error(void);
 int kair_device_arch(char* buf, int len);
 

@@ -223,6 +223,12 @@ _SIGS = {
     "kair_jpeg_roundtrip": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp],
     "kair_rgb2gray8": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],
     "kair_synth_jpeg": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp],
+    "kair_bsr_crop": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_bsr_finish": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "kair_bsr_kernels": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_long, c_vp],
+    "kair_bsr_ops": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                     c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_vp],
+    "kair_jpeg_roundtrip_var": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp],
     "kair_swin_attn_fwd": [c_vp, c_long, c_vp, c_vp, c_float, c_int, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_float, c_vp, c_long, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_long, c_long, c_int,
                            c_int, c_int, c_int, c_int, c_vp],
@@ -1062,6 +1068,104 @@ def synth_jpeg(pool, params, B, PS, is_color, outH, outL):
     pp, ps = _rows_of(params, torch.int32, 8, "synth_jpeg params")
     check(lib().kair_synth_jpeg(ptr(pool), N, C, Hs, Ws, pp, ps, B, PS, int(bool(is_color)), ptr(outH), ptr(outL),
                                 stream_ptr()), "synth_jpeg")
+
+
+def _bsr_buf(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != 3:
+        raise ValueError(f"{what}: expected a contiguous fp32 [B, 3, Hmax, Wmax] buffer")
+    return t.shape[0], t.shape[2], t.shape[3]
+
+
+def bsr_crop(pool, head, B, PS, dst):
+    """dst [B, 3, PS, PS] <- the augmented crops of head [B, >= 6] int32 {image, rnd_h, rnd_w, mode, lq_h, lq_w}
+    (kair_bsr_crop)."""
+    require_device(pool, head, dst)
+    N, C, Hs, Ws = pool.shape
+    if pool.dtype != torch.float32 or not pool.is_contiguous() or _bsr_buf(dst, "bsr_crop") != (B, PS, PS):
+        raise ValueError("bsr_crop: pool must be contiguous fp32, dst [B, 3, PS, PS]")
+    if head.shape[0] < B:
+        raise ValueError("bsr_crop: fewer parameter rows than samples")
+    hp, hs = _rows_of(head, torch.int32, 6, "bsr_crop head")
+    check(lib().kair_bsr_crop(ptr(pool), N, C, Hs, Ws, hp, hs, B, PS, ptr(dst), stream_ptr()), "bsr_crop")
+
+
+def bsr_finish(pool, head, B, PS, sf, lq, src, outL, outH):
+    """outL [B, 3, lq, lq] <- the crop of the buffer src [B, 3, PS, PS] at head's (lq_h, lq_w); outH [B, 3, lq sf, lq sf]
+    <- the aligned crop of the augmented pool patch (kair_bsr_finish)."""
+    require_device(pool, head, src, outL, outH)
+    N, C, Hs, Ws = pool.shape
+    if pool.dtype != torch.float32 or not pool.is_contiguous() or _bsr_buf(src, "bsr_finish") != (B, PS, PS):
+        raise ValueError("bsr_finish: pool must be contiguous fp32, src [B, 3, PS, PS]")
+    for t, shp in ((outL, (B, 3, lq, lq)), (outH, (B, 3, lq * sf, lq * sf))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f"bsr_finish: output must be a contiguous fp32 {shp}")
+    if head.shape[0] < B:
+        raise ValueError("bsr_finish: fewer parameter rows than samples")
+    hp, hs = _rows_of(head, torch.int32, 6, "bsr_finish head")
+    check(lib().kair_bsr_finish(ptr(pool), N, C, Hs, Ws, hp, hs, B, PS, sf, lq, ptr(src), ptr(outL), ptr(outH),
+                                stream_ptr()), "bsr_finish")
+
+
+def bsr_kernels(table, nslot, slot_stride, out):
+    """out [nslot, B, ks_max, ks_max] <- the Gaussian kernels of the blur rows of table [B, >= (nslot - 1) slot_stride + 16]
+    int32 (slot s of sample b at table[b, s * slot_stride:]); other rows' entries are left alone (kair_bsr_kernels)."""
+    require_device(table, out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 4 or out.shape[0] != nslot:
+        raise ValueError("bsr_kernels: out must be a contiguous fp32 [nslot, B, ks, ks]")
+    B = out.shape[1]
+    if table.shape[0] < B:
+        raise ValueError("bsr_kernels: fewer table rows than samples")
+    tp, ts = _rows_of(table, torch.int32, (nslot - 1) * slot_stride + 16, "bsr_kernels table")
+    check(lib().kair_bsr_kernels(tp, ts, slot_stride, nslot, B, ptr(out), out.shape[2] * out.shape[3], stream_ptr()),
+          "bsr_kernels")
+
+
+def bsr_ops(src, dst, rows, k, taps=None, seed=0, step=0, slot=0, direct=False):
+    """One slot of the blind-SR program (kair_bsr_ops): src -> dst, both [B, 3, Hmax, Wmax]; rows [B, >= 16] int32;
+    k [B, ks_max, ks_max] the slot's kernels; taps = (ih, wh, iw, ww, h_in, w_in), utils_image.bicubic_taps at x1/2 of
+    an (h_in, w_in) image on the device, for the MATLAB resize kind."""
+    require_device(src, dst, rows, k)
+    B, Hmax, Wmax = _bsr_buf(src, "bsr_ops")
+    if _bsr_buf(dst, "bsr_ops") != (B, Hmax, Wmax) or src.data_ptr() == dst.data_ptr():
+        raise ValueError("bsr_ops: src and dst must be two buffers of one shape")
+    if k.dtype != torch.float32 or not k.is_contiguous() or k.dim() != 3 or k.shape[0] < B or rows.shape[0] < B:
+        raise ValueError("bsr_ops: k must be a contiguous fp32 [B, ks, ks], rows [B, >= 16]")
+    rp, rs = _rows_of(rows, torch.int32, 16, "bsr_ops rows")
+    tp = [None, None, None, None, 0, 0, 0]
+    if taps is not None:
+        ih, wh, iw, ww, th, tw = taps
+        require_device(ih, wh, iw, ww)
+        P = ih.shape[1]
+        for t, dt, n in ((ih, torch.int32, th), (wh, torch.float32, th), (iw, torch.int32, tw), (ww, torch.float32, tw)):
+            if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != ((n + 1) // 2, P):
+                raise ValueError("bsr_ops: taps must be contiguous [ceil(n_in / 2), P] int32 indices / fp32 weights")
+        tp = [ptr(ih), ptr(wh), ptr(iw), ptr(ww), P, th, tw]
+    check(lib().kair_bsr_ops(ptr(src), ptr(dst), B, Hmax, Wmax, rp, rs, ptr(k), k.shape[1] * k.shape[2], *tp, seed, step,
+                             slot, int(direct), stream_ptr()), "bsr_ops")
+
+
+def jpeg_roundtrip_var(x, hw, w_min, quality, out, ws=None):
+    """Colour JPEG round trip of the per-sample corners of a padded batch (kair_jpeg_roundtrip_var): x, out
+    [N, 3, Hmax, Wmax] (out may be x); hw [N, >= 2] int32 {h, w}; quality int32 [N] (a table column is fine), <= 0
+    copies; w_min the caller's lower bound on the widths.  ws: the uint8 workspace (jpeg_var_workspace), or None."""
+    require_device(x, hw, quality, out, ws)
+    N, Hmax, Wmax = _bsr_buf(x, "jpeg_roundtrip_var")
+    if _bsr_buf(out, "jpeg_roundtrip_var") != (N, Hmax, Wmax):
+        raise ValueError("jpeg_roundtrip_var: x and out must have one shape")
+    if quality.dtype != torch.int32 or quality.dim() != 1 or quality.shape[0] < N or hw.shape[0] < N:
+        raise ValueError("jpeg_roundtrip_var: quality must be an int32 vector of N entries, hw [N, >= 2]")
+    hp, hs = _rows_of(hw, torch.int32, 2, "jpeg_roundtrip_var hw")
+    if ws is None:
+        ws = jpeg_var_workspace(N, Hmax, Wmax, x.device)
+    check(lib().kair_jpeg_roundtrip_var(ptr(x), N, Hmax, Wmax, hp, hs, int(w_min), ptr(quality), quality.stride(0),
+                                        ptr(out), ptr(ws), stream_ptr()), "jpeg_roundtrip_var")
+
+
+def jpeg_var_workspace(N, Hmax, Wmax, device):
+    nbytes = lib().kair_jpeg_workspace_bytes(N, 3, Hmax, Wmax)
+    if nbytes <= 0:
+        raise ValueError("jpeg_roundtrip_var: image too large")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def swin_attn_fwd(x, ldx, gamma, beta, eps, C, ln, ldln, mean, rstd, wqkv, bqkv, qkv, table, scale, O, ldo, o_ones_col,

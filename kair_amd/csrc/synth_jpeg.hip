@@ -5,6 +5,9 @@
 //
 //   kair_jpeg_roundtrip  whole images [N][1 or 3][H][W]: gray JPEG, or RGB as 4:2:0 YCbCr with the h2v2 "fancy"
 //                        upsampler; a quality per sample.
+//   kair_jpeg_roundtrip_var  the colour round trip of a padded batch [N][3][Hmax][Wmax] whose sample n is the top-left
+//                        (h, w) corner, with a quality per sample; quality 0 copies (the blind-SR program,
+//                        synth_blindsr.hip, runs a JPEG step on some samples of a batch only).
 //   kair_rgb2gray8       the two gray conversions of the loader: MATLAB rgb2ycbcr Y or OpenCV's COLOR_RGB2GRAY.
 //   kair_synth_jpeg      a batch of DatasetJPEG items in one launch: (PS + 8)^2 crop, 8-way augment, uint8, gray
 //                        conversion, JPEG round trip, second PS^2 crop at an offset in [0, 8] (so the 8 x 8 block grid
@@ -252,6 +255,28 @@ KAIR_DEV void color_px(const JpegArgs& a, const unsigned char* p0, const unsigne
   rgb[2] = clamp8(y + ((116130 * c[0] + 32768) >> 16));
 }
 
+// block counts of a PH x PW image; false when the block rows of a sample do not fit an int
+__host__ __device__ inline bool jpeg_layout(JpegArgs& a) {
+  const long bh0 = (a.PH + 7) / 8, bw0 = (a.PW + 7) / 8;
+  const long bh1 = ((a.PH + 1) / 2 + 7) / 8, bw1 = ((a.PW + 1) / 2 + 7) / 8;
+  const long nb0 = bh0 * bw0, nb1 = a.color ? bh1 * bw1 : 0, nblk = nb0 + 2 * nb1;
+  if (nblk * 64 >= (1L << 31)) return false;
+  a.bw0 = (int)bw0; a.nb0 = (int)nb0; a.bw1 = (int)bw1; a.nb1 = (int)nb1; a.nblk = (int)nblk;
+  a.gps = (int)((nblk * 8 + 255) / 256);
+  a.plane_bytes = nblk * 64;
+  return true;
+}
+
+// block rows [t0, t1) of a colour sample decoded into its workspace w: plane 0, then 1, then 2, whole blocks
+KAIR_DEV void planes_to_ws(const JpegArgs& a, const JpegGeo& g, const int* sQ, int* sT, int t0, int t1, unsigned char* w) {
+  const long o1 = (long)a.nb0 * 64, o2 = o1 + (long)a.nb1 * 64;
+  code_blocks(a, g, sQ, sT, t0, t1, [&](int pl, int i, int j0, const int (&v)[8], const int (&)[8]) {
+    unsigned char* row = w + (pl == 0 ? 0 : pl == 1 ? o1 : o2) + (long)i * ((pl ? a.bw1 : a.bw0) * 8) + j0;
+    *reinterpret_cast<uint2*>(row) = make_uint2(v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24,
+                                                v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24);
+  });
+}
+
 // gray (a.color == 0): grid = samples x gps workgroups of 256 threads = 32 blocks each; pixels go straight out.
 // whole colour images (a.ws): the same grid decodes the three planes into the workspace.
 __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const JpegArgs a) {
@@ -263,13 +288,7 @@ __global__ __launch_bounds__(256) void jpeg_blocks_kernel(const JpegArgs a) {
   __syncthreads();
   const int t0 = grp * 256, t1 = min(a.nblk * 8, t0 + 256);
   if (a.color) {
-    unsigned char* w = a.ws + (long)b * a.plane_bytes;
-    const long o1 = (long)a.nb0 * 64, o2 = o1 + (long)a.nb1 * 64;
-    code_blocks(a, g, sQ, sT, t0, t1, [&](int pl, int i, int j0, const int (&v)[8], const int (&)[8]) {
-      unsigned char* row = w + (pl == 0 ? 0 : pl == 1 ? o1 : o2) + (long)i * ((pl ? a.bw1 : a.bw0) * 8) + j0;
-      *reinterpret_cast<uint2*>(row) = make_uint2(v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24,
-                                                  v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24);
-    });
+    planes_to_ws(a, g, sQ, sT, t0, t1, a.ws + (long)b * a.plane_bytes);
     return;
   }
   if (a.par) {
@@ -359,19 +378,57 @@ __global__ __launch_bounds__(256) void rgb2gray8_kernel(const float* __restrict_
   out[t] = (float)gray_of(mode, c[0], c[1], c[2]) / 255.f;
 }
 
-constexpr long JPEG_LDS_BYTES = 150 * 1024;   // of CDNA4's 160 KB per workgroup
-
-// block counts of a PH x PW image; false when the block rows of a sample do not fit an int
-bool jpeg_layout(JpegArgs& a) {
-  const long bh0 = (a.PH + 7) / 8, bw0 = (a.PW + 7) / 8;
-  const long bh1 = ((a.PH + 1) / 2 + 7) / 8, bw1 = ((a.PW + 1) / 2 + 7) / 8;
-  const long nb0 = bh0 * bw0, nb1 = a.color ? bh1 * bw1 : 0, nblk = nb0 + 2 * nb1;
-  if (nblk * 64 >= (1L << 31)) return false;
-  a.bw0 = (int)bw0; a.nb0 = (int)nb0; a.bw1 = (int)bw1; a.nb1 = (int)nb1; a.nblk = (int)nblk;
-  a.gps = (int)((nblk * 8 + 255) / 256);
-  a.plane_bytes = nblk * 64;
-  return true;
+// kair_jpeg_roundtrip_var: the arguments with sample b's own (h, w) and block layout (the workspace stride and the grid
+// stay those of the padded size); false: quality 0, the sample is copied
+KAIR_DEV bool jpeg_var_sample(const JpegArgs& a, const int* hw, int hwstride, int b, JpegArgs& s) {
+  s = a;
+  s.PH = min(max(hw[(long)b * hwstride], 1), a.Hs);
+  s.PW = min(max(hw[(long)b * hwstride + 1], 1), a.Ws);
+  jpeg_layout(s);
+  s.gps = a.gps;
+  s.plane_bytes = a.plane_bytes;
+  return a.quality[(long)b * a.qstride] > 0;
 }
+
+__global__ __launch_bounds__(256) void jpeg_var_blocks_kernel(const JpegArgs a, const int* __restrict__ hw, int hwstride) {
+  __shared__ int sQ[128];
+  __shared__ int sT[32 * 72];
+  const int b = blockIdx.x / a.gps, grp = blockIdx.x - b * a.gps;
+  JpegArgs s;
+  if (!jpeg_var_sample(a, hw, hwstride, b, s)) return;   // uniform per workgroup, as is the next test
+  const int t0 = grp * 256, t1 = min(s.nblk * 8, t0 + 256);
+  if (t0 >= t1) return;
+  const JpegGeo g = jpeg_geo(s, b);
+  make_tables(g.q, sQ, threadIdx.x);
+  __syncthreads();
+  planes_to_ws(s, g, sQ, sT, t0, t1, a.ws + (long)b * a.plane_bytes);
+}
+
+// one thread per pixel of [N][Hmax][Wmax]; pixels outside a sample's (h, w) are left alone
+__global__ __launch_bounds__(256) void jpeg_var_finish_kernel(const JpegArgs a, const int* __restrict__ hw, int hwstride) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x, plane = (long)a.Hs * a.Ws;
+  if (t >= a.N * plane) return;
+  const int n = (int)(t / plane);
+  const long p = t - n * plane;
+  const int i = (int)(p / a.Ws), j = (int)(p - (long)i * a.Ws);
+  JpegArgs s;
+  const bool coded = jpeg_var_sample(a, hw, hwstride, n, s);
+  if (i >= s.PH || j >= s.PW) return;
+  const long o = (long)n * 3 * plane + p;
+  if (!coded) {
+    if (a.outL == a.src) return;   // in place: nothing to do
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.outL[o + c * plane] = a.src[o + c * plane];
+    return;
+  }
+  const unsigned char* w = a.ws + (long)n * a.plane_bytes;
+  int rgb[3];
+  color_px(s, w, w + (long)s.nb0 * 64, w + (long)(s.nb0 + s.nb1) * 64, i, j, rgb);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.outL[o + c * plane] = (float)rgb[c] / 255.f;
+}
+
+constexpr long JPEG_LDS_BYTES = 150 * 1024;   // of CDNA4's 160 KB per workgroup
 
 }  // namespace
 
@@ -403,6 +460,30 @@ extern "C" int kair_jpeg_roundtrip(const float* x, int N, int C, int H, int W, c
     KAIR_LAUNCH(jpeg_color_finish_kernel, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, a);
     KAIR_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int kair_jpeg_roundtrip_var(const float* x, int N, int Hmax, int Wmax, const int* hw, int hwstride, int w_min,
+                                       const int* quality, int qstride, float* out, void* workspace, void* stream) {
+  KAIR_CHECK_ARG(x && hw && quality && out && workspace, "jpeg_roundtrip_var: null pointer");
+  KAIR_CHECK_ARG(N > 0 && Hmax > 0 && Wmax > 0 && hwstride >= 2 && qstride >= 0,
+                 "jpeg_roundtrip_var: bad sizes (N %d, buffer %dx%d, hwstride %d, qstride %d)", N, Hmax, Wmax, hwstride,
+                 qstride);
+  KAIR_CHECK_ARG(w_min >= 5 && w_min <= Wmax,
+                 "jpeg_roundtrip_var: colour images need a width of at least 5 (the caller's lower bound is %d)", w_min);
+  JpegArgs a{};
+  a.src = x; a.N = N; a.C = 3; a.Hs = Hmax; a.Ws = Wmax;
+  a.quality = quality; a.qstride = qstride;
+  a.PH = Hmax; a.PW = Wmax; a.color = 1;
+  a.outL = out; a.ws = (unsigned char*)workspace;
+  KAIR_CHECK_ARG(jpeg_layout(a) && (long)N * a.gps < (1L << 31) && ((long)N * Hmax * Wmax + 255) / 256 < (1L << 31),
+                 "jpeg_roundtrip_var: too many workgroups");
+  hipStream_t s = (hipStream_t)stream;
+  KAIR_LAUNCH(jpeg_var_blocks_kernel, dim3((unsigned)((long)N * a.gps)), dim3(256), 0, s, a, hw, hwstride);
+  KAIR_CHECK_LAUNCH();
+  KAIR_LAUNCH(jpeg_var_finish_kernel, dim3((unsigned)(((long)N * Hmax * Wmax + 255) / 256)), dim3(256), 0, s, a, hw,
+              hwstride);
+  KAIR_CHECK_LAUNCH();
   return 0;
 }
 

@@ -39,6 +39,24 @@ reference, or a list to draw from uniformly: blind CAR, an extension) and one ra
 second H_size^2 crop sits at random offsets rh2, rw2 in [0, 8] or at (0, 0).  One launch (kair_synth_jpeg,
 csrc/synth_jpeg.hip) does the crop, augment, uint8 and gray conversion, the JPEG round trip and the second crop.
 `last_params` is the [B, 8] int32 table {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2, rw2}.
+
+task="blindsr" makes DatasetBlindSR batches (data/dataset_blindsr.py; the BSRGAN degradation of BSRNet / BSRGAN and the
+real-world SwinIR) from a 3-channel pool:
+
+    synth = PatchSynth(pool, task="blindsr", scale=4, H_size=256, lq_patchsize=64, seed=0)
+    L, H = synth.next(32)                        # [B, 3, 64, 64], [B, 3, 256, 256]
+
+Per sample, in this order: the image, rnd_h and rnd_w of the H_size^2 crop, the augment mode, then every draw of
+utils_blindsr.draw_bsrgan (that module's docstring lists them) from the same random.Random, so DatasetBlindSR with that
+generator takes identical decisions.  The pixels are made by a fixed sequence of launches whatever was drawn
+(csrc/synth_blindsr.hip, kair_jpeg_roundtrip_var): crop + augment, the blur kernels, slot 0 (the optional x1/2
+pre-downscale), slots 1-6 (an op launch and a JPEG launch pair each; whichever does not apply to a sample copies it or
+leaves it), the final JPEG, the two crops.  `last_params` is the [B, 136] int32 program table: columns 0-5 {image,
+rnd_h, rnd_w, mode, lq_h, lq_w} (lq_* the corner of the L crop in the degraded image; H is cut at lq_* x scale),
+6-7 unused, then 8 slots of 16 columns, slot s at 8 + 16 s: {op, h_in, w_in, h_out, w_out, i0, i1, quality} and eight
+float32 bits, as utils_blindsr's docstring describes them (`last_params[:, 8:].view(B, 8, 16)` is the stack of the
+samples' `prog` tables).  debug_stages=True makes next() return (L, H, stages): stages[0] the cropped patches and
+stages[1 + s] the buffer after slot s, each (tensor [B, 3, H_size, H_size], [(h, w)] per sample), for the tests.
 """
 import math
 import random
@@ -46,12 +64,17 @@ import random
 import torch
 
 from .. import _hip as H
+from ..utils import utils_blindsr as blindsr
 from ..utils import utils_image as util
+
+
+BSR_COLS = 8 + blindsr.NSLOT * blindsr.NCOL   # the blind-SR program table's row
 
 
 class PatchSynth:
     def __init__(self, pool, task="sr", scale=4, H_size=96, sigma=25, seed=0, rank=0, world=1, scales=(1, 2, 3, 4),
-                 sigma_max=25, kernel_size=25, kernel_bank=None, trunc8=False, quality_factor=40, is_color=False):
+                 sigma_max=25, kernel_size=25, kernel_bank=None, trunc8=False, quality_factor=40, is_color=False,
+                 lq_patchsize=64, debug_stages=False):
         if pool.dim() != 4 or not pool.is_cuda:
             raise ValueError("PatchSynth: pool must be a device tensor [N, C, Hs, Ws]")
         self.task = task
@@ -79,6 +102,15 @@ class PatchSynth:
                 raise ValueError("PatchSynth: task 'jpeg' needs a 1- or 3-channel pool (3 with is_color)")
             if H_size + 8 > min(pool.shape[-2:]):
                 raise ValueError(f"PatchSynth: task 'jpeg' crops H_size + 8 = {H_size + 8}; the pool images are smaller")
+        if task == "blindsr":
+            blindsr.check_sizes(H_size, scale, lq_patchsize)
+            if pool.shape[1] != 3:
+                raise ValueError("PatchSynth: task 'blindsr' needs a 3-channel pool (the JPEG steps are colour)")
+            if H_size // 8 < 5:
+                raise ValueError("PatchSynth: task 'blindsr' needs H_size >= 40 (a working image of H_size / 8 must "
+                                 "keep the colour JPEG's minimum width of 5)")
+            self.lq, self.bsr_sf, self.debug_stages = int(lq_patchsize), int(scale), bool(debug_stages)
+            self._noise_off = False   # tests only: utils_blindsr.draw_bsrgan(noise_off=True)
         self.sf = scale if task == "sr" else 1
         Hs, Ws = pool.shape[-2:]
         if task == "sr":   # modcrop (dataset_sr.py:51)
@@ -100,6 +132,10 @@ class PatchSynth:
             iw, ww = util.bicubic_taps(self.Ws, self.Ws // self.sf, 1.0 / self.sf)
             self.taps_h = (ih.to(dev), wh.to(dev))
             self.taps_w = (iw.to(dev), ww.to(dev))
+        elif task == "blindsr":
+            ih, wh = util.bicubic_taps(self.PS, self.PS // 2, 0.5)   # the MATLAB x1/2 of slot 0
+            self.taps_half = (ih.to(dev), wh.to(dev), ih.to(dev), wh.to(dev), self.PS, self.PS)
+            self._bsr_ws = None
         elif task not in ("dn", "usrnet", "jpeg"):
             raise ValueError(task)
         self._par_host = None
@@ -135,6 +171,8 @@ class PatchSynth:
         every step never blocks the host on the device.  task "usrnet": (L, H, k, sf, sigma)."""
         if self.task == "usrnet":
             return self._next_usr(B)
+        if self.task == "blindsr":
+            return self._next_blindsr(B)
         dev = self.pool.device
         jpeg = self.task == "jpeg"
         host = self._draw_jpeg(B) if jpeg else self.draw(B)
@@ -229,6 +267,63 @@ class PatchSynth:
         self.step += 1
         self.last_params = par
         return Lp, Hp, k, sf, fl[:, 3].reshape(B, 1, 1, 1).contiguous()
+
+    def _draw_blindsr(self, B):
+        """Host draws of the next blind-SR batch: the [B, 136] int32 program table (module docstring)."""
+        tab = torch.zeros(B, BSR_COLS, dtype=torch.int32)
+        for b in range(B):
+            img = self._next_index()
+            rh = self.rng.randint(0, self.Hs - self.PS)
+            rw = self.rng.randint(0, self.Ws - self.PS)
+            mode = self.rng.randint(0, 7)
+            prog, lh, lw = blindsr.draw_bsrgan(self.rng, self.PS, self.bsr_sf, self.lq, self._noise_off)
+            tab[b, :6] = torch.tensor([img, rh, rw, mode, lh, lw], dtype=torch.int32)
+            tab[b, 8:] = torch.from_numpy(prog.reshape(-1))
+        return tab
+
+    def _next_blindsr(self, B):
+        dev = self.pool.device
+        host = self._draw_blindsr(B)
+        if self._par_host is None or self._par_host.shape[0] < B:
+            self._par_host = torch.empty(B, BSR_COLS, dtype=torch.int32).pin_memory()
+            self._par_ev = None
+        if self._par_ev is not None:
+            self._par_ev.synchronize()   # the previous batch's copy has read the staging buffer
+        self._par_host[:B].copy_(host)
+        par = self._par_host[:B].to(dev, non_blocking=True)
+        self._par_ev = torch.cuda.Event()
+        self._par_ev.record()
+        PS, S, W = self.PS, blindsr.NSLOT, blindsr.NCOL
+        if self._bsr_ws is None or self._bsr_ws[0] != B:
+            self._bsr_ws = (B, torch.empty(B, 3, PS, PS, device=dev), torch.empty(B, 3, PS, PS, device=dev),
+                            torch.empty(S, B, 25, 25, device=dev), H.jpeg_var_workspace(B, PS, PS, dev))
+        _, a, b, kern, jws = self._bsr_ws
+        slot = lambda s: par[:, 8 + W * s:8 + W * (s + 1)]   # noqa: E731
+        stages = []
+
+        def keep(buf, hw_cols):
+            if self.debug_stages:
+                stages.append((buf.clone(), [tuple(r) for r in host[:, hw_cols[0]:hw_cols[1]].tolist()]))
+
+        w_min = PS // 8
+        H.bsr_crop(self.pool, par, B, PS, a)
+        keep(a, (8 + 1, 8 + 3))
+        H.bsr_kernels(par[:, 8:], S, W, kern)
+        for s in range(S - 1):   # slot 0 the pre-downscale, 1-6 the drawn ops; a <-> b
+            H.bsr_ops(a, b, slot(s), kern[s], self.taps_half if s == 0 else None, self.seed, self.step, s)
+            if s:
+                H.jpeg_roundtrip_var(b, slot(s)[:, 3:5], w_min, slot(s)[:, 7], b, jws)
+            a, b = b, a
+            keep(a, (8 + W * s + 3, 8 + W * s + 5))
+        s = S - 1   # the final JPEG, in place
+        H.jpeg_roundtrip_var(a, slot(s)[:, 3:5], w_min, slot(s)[:, 7], a, jws)
+        keep(a, (8 + W * s + 3, 8 + W * s + 5))
+        Lp = torch.empty(B, 3, self.lq, self.lq, device=dev)
+        Hp = torch.empty(B, 3, self.lq * self.bsr_sf, self.lq * self.bsr_sf, device=dev)
+        H.bsr_finish(self.pool, par, B, PS, self.bsr_sf, self.lq, a, Lp, Hp)
+        self.step += 1
+        self.last_params = par
+        return (Lp, Hp, stages) if self.debug_stages else (Lp, Hp)
 
     def next_dict(self, B):
         """The next USRNet batch as the dict ModelPlain4.feed_data reads (sf an int64 tensor [B])."""

@@ -1,7 +1,8 @@
 """Dataset factory (mirror of /root/reference/data/select_dataset.py:12-100) for the datasets that
 feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1), 'sr' (DatasetSR, configs 2/4/5),
-'usrnet' (DatasetUSRNet, config 3) and 'jpeg' (DatasetJPEG, the JPEG artifact-reduction SwinIR of
-train_swinir_car_jpeg.json).
+'usrnet' (DatasetUSRNet, config 3), 'jpeg' (DatasetJPEG, the JPEG artifact-reduction SwinIR of
+train_swinir_car_jpeg.json) and 'blindsr' (DatasetBlindSR, the BSRGAN degradation of
+train_bsrgan_x4_psnr.json and train_swinir_sr_realworld_x4_psnr.json).
 Other dataset types are off the path and raise NotImplementedError naming the type."""
 
 
@@ -15,6 +16,8 @@ def define_Dataset(dataset_opt):
         from .dataset_usrnet import DatasetUSRNet as D
     elif t == "jpeg":
         from .dataset_jpeg import DatasetJPEG as D
+    elif t in ("blindsr", "bsrnet", "bsrgan"):
+        from .dataset_blindsr import DatasetBlindSR as D
     else:
-        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr, usrnet, jpeg).")
+        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, sr, usrnet, jpeg, blindsr).")
     return D(dataset_opt)
