@@ -705,12 +705,20 @@ int kair_rowgemm_lnbwd(const void* A, long lda, long M, int K, const void* W, co
  * ww/iw [Ws/sf][P] from calculate_weights_indices :880-932, source indices already reflected),
  * cropped at (rnd_h, rnd_w) and augmented; H the aligned sf x larger crop.
  * kair_synth_dn replaces DatasetDnCNN.__getitem__ train branch (data/dataset_dncnn.py:50-75):
- * L = H + sigma * N(0,1) (sigma = sigma_255 / 255), Philox-4x32-10 normals keyed by (seed, step). */
+ * L = H + sigma * N(0,1) (sigma = sigma_255 / 255), Philox-4x32-10 normals keyed by (seed, step).
+ * kair_synth_dn_map replaces DatasetFDnCNN.__getitem__ train branch (data/dataset_fdncnn.py; FDnCNN / DRUNet): params
+ * rows of pstride >= 5 ints {image, rnd_h, rnd_w, mode, ...} (image / rnd_* clamped into the pool of N images), the
+ * sample's level sigma_b (= sigma_255 / 255) as float32 bits in column scol >= 4.  outH [B][C][PS][PS] as
+ * kair_synth_dn's; outL [B][C+1][PS][PS]: channels < C are H + sigma_b * N(0,1), channel C is the constant sigma_b.
+ * The normals are kair_synth_dn's stream (same key, counter = the element index in the [B][C][PS][PS] block), so a
+ * table of equal levels gives kair_synth_dn's L bit for bit; sigma_b = 0 leaves L[:, :C] = H. */
 int kair_synth_sr(const float* pool, int C, int Hs, int Ws, const int* params, int B, int PS, int sf,
                   const float* wh, const int* ih, const float* ww, const int* iw, int P, float* outH,
                   float* outL, void* stream);
 int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int* params, int B, int PS, float sigma,
                   unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
+int kair_synth_dn_map(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
+                      int PS, unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
 
 /* ---- USRNet training data (csrc/synth_usr.hip; DatasetUSRNet.__getitem__, data/dataset_usrnet.py:46-113) --------
  * kair_usr_gauss_kernels: B blur kernels [B][ksize][ksize] fp32, utils_sisr.gen_kernel (utils_sisr.py:172-215) with

@@ -214,6 +214,8 @@ _SIGS = {
                       c_vp],
     "kair_synth_dn": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_float, ctypes.c_ulonglong, ctypes.c_ulonglong,
                       c_vp, c_vp, c_vp],
+    "kair_synth_dn_map": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.c_ulonglong,
+                          ctypes.c_ulonglong, c_vp, c_vp, c_vp],
     "kair_usr_gauss_kernels": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp],
     "kair_synth_usr": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
                        c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_int, c_vp],
@@ -946,6 +948,23 @@ def synth_dn(pool, params, B, PS, sigma, seed, step, outH, outL):
     N, C, Hs, Ws = pool.shape
     check(lib().kair_synth_dn(ptr(pool), C, Hs, Ws, ptr(params), B, PS, sigma, seed, step, ptr(outH), ptr(outL),
                               stream_ptr()), "synth_dn")
+
+
+def synth_dn_map(pool, params, B, PS, seed, step, outH, outL, sigma_col=4):
+    """FDnCNN / DRUNet batch (kair_synth_dn_map): params [B, >= 5] int32 {image, rnd_h, rnd_w, mode} plus the float32
+    bits of the sample's sigma / 255 in column sigma_col; outH [B, C, PS, PS], outL [B, C + 1, PS, PS]."""
+    require_device(pool, params, outH, outL)
+    N, C, Hs, Ws = pool.shape
+    if pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise ValueError("synth_dn_map: pool must be contiguous fp32")
+    if params.shape[0] < B:
+        raise ValueError("synth_dn_map: fewer parameter rows than samples")
+    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C + 1, PS, PS))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f"synth_dn_map: output must be a contiguous fp32 {shp}")
+    pp, ps = _rows_of(params, torch.int32, max(5, sigma_col + 1), "synth_dn_map params")
+    check(lib().kair_synth_dn_map(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
+                                  stream_ptr()), "synth_dn_map")
 
 
 def _rows_of(t, dtype, ncol, what):

@@ -2,6 +2,8 @@
 //   DatasetSR.__getitem__    data/dataset_sr.py:35-92   (modcrop'd H, MATLAB-bicubic x1/sf L of the
 //                                                        whole image, aligned random crop, 8-way augment)
 //   DatasetDnCNN.__getitem__ data/dataset_dncnn.py:50-75 (random crop, 8-way augment, L = H + sigma N)
+//   DatasetFDnCNN.__getitem__ data/dataset_fdncnn.py    (the same with one sigma per sample and the noise-level
+//                                                        map as L's last channel)
 // for a whole batch in one launch, reading an image pool resident in HBM (fp32 NCHW, [0, 1]).
 //
 // The 8 augment modes: aug_src in synth_common.h.
@@ -148,6 +150,38 @@ __global__ __launch_bounds__(256) void synth_dn_kernel(const float* __restrict__
   outL[t] = h + sigma * normal_at((unsigned long long)t, seed, step);
 }
 
+// DatasetFDnCNN: H = aug(crop(pool)); L = [H + sigma_b * N(0, 1) | sigma_b], sigma_b the float in column scol of
+// sample b's parameter row.  One thread per outL element, so both outputs are stored at consecutive addresses by
+// consecutive lanes (outH within each channel plane) and the augment's gather stays on the pool read.  The normals'
+// counter is the element index of the [B][C][PS][PS] noisy block -- synth_dn_kernel's, whose L an all-equal table
+// reproduces bit for bit.  image / rnd_h / rnd_w are clamped into the pool.
+__global__ __launch_bounds__(256) void synth_dn_map_kernel(const float* __restrict__ pool, int N, int C, int Hs, int Ws,
+                                                           const int* __restrict__ par, int pstride, int scol, int B,
+                                                           int PS, unsigned long long seed, unsigned long long step,
+                                                           float* __restrict__ outH, float* __restrict__ outL) {
+  const long n = (long)B * (C + 1) * PS * PS;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int j = (int)(t % PS);
+  long r = t / PS;
+  const int i = (int)(r % PS);
+  r /= PS;
+  const int c = (int)(r % (C + 1)), b = (int)(r / (C + 1));
+  const int* pr = par + (long)b * pstride;   // {image, rnd_h, rnd_w, mode}, ..., [scol] = float bits of sigma_b
+  const float sigma = __int_as_float(pr[scol]);
+  if (c == C) {
+    outL[t] = sigma;
+    return;
+  }
+  const int img = min(max(pr[0], 0), N - 1), rh = min(max(pr[1], 0), Hs - PS), rw = min(max(pr[2], 0), Ws - PS);
+  int si, sj;
+  aug_src(pr[3] & 7, i, j, PS, si, sj);
+  const float h = pool[(((long)img * C + c) * Hs + rh + si) * Ws + rw + sj];
+  const long u = (((long)b * C + c) * PS + i) * PS + j;
+  outH[u] = h;
+  outL[t] = h + sigma * normal_at((unsigned long long)u, seed, step);
+}
+
 long nblocks(long n) { return (n + 255) / 256; }
 
 }  // namespace
@@ -187,6 +221,21 @@ extern "C" int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int
   const long total = (long)B * C * PS * PS;
   KAIR_LAUNCH(synth_dn_kernel, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, C, Hs, Ws,
                      (const int4*)params, B, PS, sigma, seed, step, outH, outL);
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kair_synth_dn_map(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol,
+                                 int B, int PS, unsigned long long seed, unsigned long long step, float* outH,
+                                 float* outL, void* stream) {
+  KAIR_CHECK_ARG(pool && params && outH && outL, "synth_dn_map: null pointer");
+  KAIR_CHECK_ARG(N > 0 && C > 0 && B > 0 && PS > 0 && PS <= Hs && PS <= Ws, "synth_dn_map: bad sizes");
+  KAIR_CHECK_ARG(pstride >= 5 && scol >= 4 && scol < pstride, "synth_dn_map: level column %d outside rows of %d ints",
+                 scol, pstride);
+  const long total = (long)B * (C + 1) * PS * PS;
+  KAIR_CHECK_ARG(nblocks(total) < (1L << 31), "synth_dn_map: too many elements");
+  KAIR_LAUNCH(synth_dn_map_kernel, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, N, C, Hs, Ws,
+                     params, pstride, scol, B, PS, seed, step, outH, outL);
   KAIR_CHECK_LAUNCH();
   return 0;
 }

@@ -57,6 +57,18 @@ rnd_h, rnd_w, mode, lq_h, lq_w} (lq_* the corner of the L crop in the degraded i
 float32 bits, as utils_blindsr's docstring describes them (`last_params[:, 8:].view(B, 8, 16)` is the stack of the
 samples' `prog` tables).  debug_stages=True makes next() return (L, H, stages): stages[0] the cropped patches and
 stages[1 + s] the buffer after slot s, each (tensor [B, 3, H_size, H_size], [(h, w)] per sample), for the tests.
+
+task="fdncnn" makes DatasetFDnCNN batches (data/dataset_fdncnn.py) for FDnCNN and DRUNet: the noisy patch with its
+noise-level map as the last channel.
+
+    synth = PatchSynth(pool, task="fdncnn", H_size=128, sigma=(0, 50), seed=0)
+    L, H = synth.next(64)                        # [B, C + 1, 128, 128], [B, C, 128, 128]
+    model.feed_data(synth.next_dict(64))         # the dict ModelPlain.feed_data reads
+
+Per sample, in this order: the image, rnd_h, rnd_w, the augment mode, then sigma = rng.uniform(min, max).  One launch
+(kair_synth_dn_map, csrc/synth.hip) does the crop, the augment, the per-sample AWGN (kair_synth_dn's Philox normals) and
+the map channel.  `last_params` is the [B, 5] int32 table {image, rnd_h, rnd_w, mode} plus the float32 bits of
+sigma / 255 (`last_params[:, 4:].view(torch.float32)`).
 """
 import math
 import random
@@ -111,6 +123,11 @@ class PatchSynth:
                                  "keep the colour JPEG's minimum width of 5)")
             self.lq, self.bsr_sf, self.debug_stages = int(lq_patchsize), int(scale), bool(debug_stages)
             self._noise_off = False   # tests only: utils_blindsr.draw_bsrgan(noise_off=True)
+        if task == "fdncnn":
+            self.sigma_range = tuple(float(v) for v in sigma) if isinstance(sigma, (tuple, list)) else (float(sigma),) * 2
+            if len(self.sigma_range) != 2 or not 0 <= self.sigma_range[0] <= self.sigma_range[1]:
+                raise ValueError(f"PatchSynth: task 'fdncnn' takes sigma as (min, max), 0 <= min <= max (got {sigma!r})")
+            sigma = self.sigma_range[1]
         self.sf = scale if task == "sr" else 1
         Hs, Ws = pool.shape[-2:]
         if task == "sr":   # modcrop (dataset_sr.py:51)
@@ -136,7 +153,7 @@ class PatchSynth:
             ih, wh = util.bicubic_taps(self.PS, self.PS // 2, 0.5)   # the MATLAB x1/2 of slot 0
             self.taps_half = (ih.to(dev), wh.to(dev), ih.to(dev), wh.to(dev), self.PS, self.PS)
             self._bsr_ws = None
-        elif task not in ("dn", "usrnet", "jpeg"):
+        elif task not in ("dn", "usrnet", "jpeg", "fdncnn"):
             raise ValueError(task)
         self._par_host = None
         self._par_ev = None
@@ -174,8 +191,8 @@ class PatchSynth:
         if self.task == "blindsr":
             return self._next_blindsr(B)
         dev = self.pool.device
-        jpeg = self.task == "jpeg"
-        host = self._draw_jpeg(B) if jpeg else self.draw(B)
+        jpeg, fdn = self.task == "jpeg", self.task == "fdncnn"
+        host = self._draw_jpeg(B) if jpeg else self._draw_fdncnn(B) if fdn else self.draw(B)
         if self._par_host is None or self._par_host.shape[0] < B:
             self._par_host = torch.empty(B, host.shape[1], dtype=torch.int32).pin_memory()
             self._par_ev = None
@@ -189,11 +206,13 @@ class PatchSynth:
         Co = (3 if self.is_color else 1) if jpeg else self.C
         if out is None:
             Hp = torch.empty(B, Co, self.PS, self.PS, device=dev)
-            Lp = torch.empty(B, Co, ls, ls, device=dev)
+            Lp = torch.empty(B, Co + 1 if fdn else Co, ls, ls, device=dev)
         else:
             Lp, Hp = out
         if jpeg:
             H.synth_jpeg(self.pool, par, B, self.PS, self.is_color, Hp, Lp)
+        elif fdn:
+            H.synth_dn_map(self.pool, par, B, self.PS, self.seed, self.step, Hp, Lp)
         elif self.task == "sr":
             H.synth_sr(self.pool, par, B, self.PS, self.sf, self.taps_h, self.taps_w, Hp, Lp)
         else:
@@ -201,6 +220,20 @@ class PatchSynth:
         self.step += 1
         self.last_params = par
         return Lp, Hp
+
+    def _draw_fdncnn(self, B):
+        """Host draws of the next FDnCNN / DRUNet batch: [B, 5] int32 {image, rnd_h, rnd_w, mode, bits of sigma / 255}."""
+        ints = torch.zeros(B, 5, dtype=torch.int32)
+        lev = torch.zeros(B, 1, dtype=torch.float32)
+        for b in range(B):
+            img = self._next_index()
+            rh = self.rng.randint(0, self.Hs - self.PS)
+            rw = self.rng.randint(0, self.Ws - self.PS)
+            mode = self.rng.randint(0, 7)
+            lev[b, 0] = self.rng.uniform(*self.sigma_range) / 255.0
+            ints[b, :4] = torch.tensor([img, rh, rw, mode], dtype=torch.int32)
+        ints[:, 4:] = lev.view(torch.int32)
+        return ints
 
     def _draw_jpeg(self, B):
         """Host draws of the next JPEG batch: [B, 8] int32 {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2, rw2}."""
@@ -326,9 +359,13 @@ class PatchSynth:
         return (Lp, Hp, stages) if self.debug_stages else (Lp, Hp)
 
     def next_dict(self, B):
-        """The next USRNet batch as the dict ModelPlain4.feed_data reads (sf an int64 tensor [B])."""
+        """The next USRNet batch as the dict ModelPlain4.feed_data reads (sf an int64 tensor [B]); task "fdncnn": the
+        {"L", "H"} dict ModelPlain.feed_data reads."""
+        if self.task == "fdncnn":
+            L, Hh = self.next(B)
+            return {"L": L, "H": Hh}
         if self.task != "usrnet":
-            raise ValueError("PatchSynth.next_dict: task 'usrnet' only")
+            raise ValueError("PatchSynth.next_dict: tasks 'usrnet' and 'fdncnn' only")
         L, Hh, k, sf, sigma = self._next_usr(B)
         return {"L": L, "H": Hh, "k": k, "sf": torch.full((B,), sf, dtype=torch.int64), "sigma": sigma}
 

@@ -2,8 +2,8 @@
 
 `opt['netG']['net_type']` selects the network; constructor kwargs are taken from opt['netG'] under
 the reference's key names, and init_weights() runs when opt['is_train'] (select_network.py:268-272).
-Networks on the MI355X path: swinir, dncnn, fdncnn, rrdb, rrdbnet, usrnet.  Everything else the
-reference's define_G knows (ffdnet, srmd, dpsr, msrresnet*, imdn, drunet, vrt, rvrt, ...) is out of
+Networks on the MI355X path: swinir, dncnn, fdncnn, rrdb, rrdbnet, usrnet, drunet.  Everything else the
+reference's define_G knows (ffdnet, srmd, dpsr, msrresnet*, imdn, vrt, rvrt, ...) is out of
 scope for this build and raises NotImplementedError naming the type.
 """
 import functools
@@ -13,7 +13,7 @@ from torch.nn import init
 
 logger = logging.getLogger("kair_amd")
 
-_ON_PATH = ("swinir", "dncnn", "fdncnn", "rrdb", "rrdbnet", "usrnet")
+_ON_PATH = ("swinir", "dncnn", "fdncnn", "rrdb", "rrdbnet", "usrnet", "drunet")
 
 
 def define_G(opt):
@@ -45,6 +45,10 @@ def define_G(opt):
         net = USRNet(n_iter=o["n_iter"], h_nc=o["h_nc"], in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"],
                      act_mode=o["act_mode"], downsample_mode=o["downsample_mode"], upsample_mode=o["upsample_mode"],
                      **ek)
+    elif t == "drunet":
+        from .network_unet import UNetRes
+        net = UNetRes(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], act_mode=o["act_mode"],
+                      downsample_mode=o["downsample_mode"], upsample_mode=o["upsample_mode"], **ek)
     else:
         raise NotImplementedError("netG [{:s}] is not on the kair_amd MI355X path (supported: {})".format(
             t, ", ".join(_ON_PATH)))
@@ -57,7 +61,7 @@ def define_G(opt):
     return net
 
 
-_X3_NETS = ("swinir", "rrdbnet", "rrdb", "usrnet")   # networks with a split-fp16 (fp32x3) engine
+_X3_NETS = ("swinir", "rrdbnet", "rrdb", "usrnet", "drunet")   # networks with a split-fp16 (fp32x3) engine
 _X3_DEFAULT_NETS = ("swinir", "rrdbnet", "rrdb")     # ... whose fp32 option files get it by default
 
 
@@ -75,8 +79,8 @@ def compute_dtype_of(opt):
                                             pairs, ~2^-21 relative -- it passes the exact-fp32 engine's oracle
                                             bars, tests/test_x3_gpu.py; RRDBNet / RRDB: tests/test_full_configs_gpu.py
                                             test_c5_rrdbnet_full[fp32x3]), else 'fp32' (exact-fp32 MFMA; USRNet
-                                            has an fp32x3 engine, tests/test_usrnet_x3_gpu.py, on explicit request
-                                            only)."""
+                                            and DRUNet have an fp32x3 engine, tests/test_usrnet_x3_gpu.py and
+                                            tests/test_drunet_gpu.py, on explicit request only)."""
     o = opt["netG"]
     if o.get("compute_dtype"):
         if o["compute_dtype"] not in ("bf16", "fp32", "fp32x3"):

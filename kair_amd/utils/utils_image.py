@@ -227,6 +227,17 @@ def augment_img_tensor4(img, mode=0):
     raise ValueError(mode)
 
 
+def add_noise_map(x, sigma_255):
+    """[B, C, H, W] -> [B, C + 1, H, W]: the noise-level map sigma_255 / 255 as the last channel, the input of the
+    FDnCNN / DRUNet denoisers (`net(add_noise_map(img, 25))`).  sigma_255: a number, or a tensor of B levels."""
+    B, _, H, W = x.shape
+    if torch.is_tensor(sigma_255):
+        m = (sigma_255.to(device=x.device, dtype=x.dtype) / 255.0).reshape(-1, 1, 1, 1).expand(B, 1, H, W)
+    else:
+        m = x.new_full((B, 1, H, W), float(sigma_255) / 255.0)
+    return torch.cat((x, m), dim=1)
+
+
 def modcrop(img_in, scale):
     img = np.copy(img_in)
     if img.ndim not in (2, 3):
