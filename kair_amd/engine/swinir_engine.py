@@ -16,14 +16,13 @@ The program is launch-only (no host syncs, no allocation after planning), so a w
 step can be captured in a HIP graph (kair_amd/engine/trainer.py).
 """
 import contextlib
-import math
-import os
 
 import torch
 
 from .. import _hip as H
 from .base import EngineBase, _Conv, _rup, drop_path_scales, lease_grads
 from .plans import Lease, autograd_mode, plan_mode
+from .swinir_tail import make_tail
 
 WINDOW_SIZES = (7, 8)    # the window sides the attention kernels are built for
 
@@ -178,7 +177,7 @@ class SwinIREngine(EngineBase):
 
     def __init__(self, net, compute_dtype="bf16", split_conv=True, fused_blocks=True, fused_mlp=None,
                  split_linear=None, fused_mlp_bwd=False, side_stream=True, side_ctas=None, side_priority=0,
-                 split_act=True, conv_wr=True, head_pad=None, grouped_wgrad=None):
+                 split_act=True, conv_wr=True, head_pad=None, grouped_wgrad=None, x3_grouped=True, x3_lnfuse=False):
         """split_conv (bf16 only): forward 3x3 convs multiply hi/lo bf16 weight pairs (_Conv), i.e.
         see the fp32 master weights to ~16 bits; split_linear does the same for the linears of the
         fused block kernels (_Lin, pack kind 12).
@@ -272,38 +271,7 @@ class SwinIREngine(EngineBase):
             self.rstb.append((blks, _resi(self, layer.conv)))
         self.norm = net.norm
         self.cab = _resi(self, net.conv_after_body)
-        nf = 64
-        self.last_narrow_x3 = False
-        if self.upsampler == "pixelshuffle":
-            self.cbu = _Conv(self, net.conv_before_upsample[0], nf, self.Cp, wr=self.conv_wr)
-            self.ups = []
-            # split_act: a0 / the upsampled activations are stored as [hi | lo] pairs (128 channels), read by
-            # the upsampling convs through weights tied over both halves (the halo kernel skips lo . lo)
-            for m in net.upsample:
-                if isinstance(m, torch.nn.Conv2d):   # output channels sub-pixel-major (PSHUF_SPM)
-                    self.ups.append(_Conv(self, m, m.out_channels, nf, n_perm=m.out_channels // nf,
-                                          tied_in=self.split_act, fwd_cip=2 * nf if self.split_act else None,
-                                          wr=self.conv_wr))
-            self.ups_r = [int(math.isqrt(c.Co // nf)) for c in self.ups]
-            # conv_last 64 -> in_ch on the narrow-output kernels (bf16 engine; HR width a multiple of 16)
-            # (per call: the HR width must be a multiple of 64, else the implicit-GEMM path runs)
-            self.last_narrow = self.tdt == torch.bfloat16 and self.split_conv and self.in_ch <= 4
-            self.last = _Conv(self, net.conv_last, 16, nf, narrow=self.last_narrow)
-            # ... and their fp32x3 forms (csrc/tail.hip *_x3: fp16 pairs of the fp32 operands, as kair_gemm_nt_x3)
-            self.last_narrow_x3 = self.x3 and self.in_ch <= 4
-        elif self.upsampler == "pixelshuffledirect":
-            conv = net.upsample[0]
-            self.ups_r = [self.scale]
-            self.up1 = _Conv(self, conv, _rup(conv.out_channels, 16), self.Cp)
-        elif self.upsampler == "nearest+conv":   # x4: two nearest x2 + conv + LeakyReLU 0.2, conv_hr, conv_last
-            self.cbu = _Conv(self, net.conv_before_upsample[0], nf, self.Cp)
-            self.nup = [_Conv(self, net.conv_up1, nf, nf), _Conv(self, net.conv_up2, nf, nf)]
-            self.hrc = _Conv(self, net.conv_hr, nf, nf)
-            self.last = _Conv(self, net.conv_last, 16, nf)
-        elif self.upsampler in (None, ""):        # denoising / JPEG: E = x + conv_last(res)
-            self.last = _Conv(self, net.conv_last, 16, self.Cp)
-        else:
-            raise NotImplementedError(self.upsampler)
+        self.tail = make_tail(self, net)   # the reconstruction tail of net.upsampler (swinir_tail.py)
         self.blocks = [b for blks, _ in self.rstb for b in blks]
         # Swin-block weight gradients: deferred to the end of each RSTB and issued as ONE grouped
         # launch (kair_wgrad_grouped: 4 linears x depth blocks) where the bf16 TN ring takes the shapes;
@@ -337,14 +305,14 @@ class SwinIREngine(EngineBase):
         if side_ctas is None:
             side_ctas = 192 if self.x3 else 0
         # fp32x3: an RSTB's deferred block weight gradients as ONE grouped TN-ring launch + one grouped finalize
-        # (kair_wgrad_grouped with fp16-pair jobs) instead of a launch pair per linear (KAIR_X3_GROUPED=0: A/B)
-        self.x3_grouped = self.x3_side and os.environ.get("KAIR_X3_GROUPED", "1") != "0"
+        # (kair_wgrad_grouped with fp16-pair jobs) instead of a launch pair per linear (x3_grouped=False: A/B)
+        self.x3_grouped = self.x3_side and bool(x3_grouped)
         # fp32x3: the LayerNorm backwards fused into the qkv / fc1 input-gradient GEMMs' epilogue (kair_gemm_nt_x3_lnbwd,
-        # KAIR_X3_LNFUSE=1).  Off by default: measured slower (B = 32 660 -> 614, B = 4 349 -> 340 patches/s,
+        # x3_lnfuse=True).  Off by default: measured slower (B = 32 660 -> 614, B = 4 349 -> 340 patches/s,
         # profiles/r06_x3_lnfuse_ab.txt) -- the LayerNorm backward's own traffic (x, D read, D and its operand copy
         # written) stays and now runs in the ring's epilogue intervals, in 64-row tiles (the 128-row form spills)
         self.x3_lnfuse = (self.x3 and self.Cp == 192 and self.C % 4 == 0 and not self.rowgemm and not fused_mlp_bwd and
-                          os.environ.get("KAIR_X3_LNFUSE", "0") == "1")
+                          bool(x3_lnfuse))
         self.side_ctas = int(side_ctas)
         # '1conv' weight gradients on the tap-per-tile ring (bf16 copies of G and the conv input)
         self.conv_tap = self.tdt == torch.bfloat16 and self.Cp == 192 and self.C % 4 == 0
@@ -355,17 +323,7 @@ class SwinIREngine(EngineBase):
         between consecutive groups.  Each group is contiguous in registration order, so the data-
         parallel trainer can all-reduce it as one bucket while the rest of backward runs."""
         net = self.net_ref()
-        tail = list(net.norm.parameters()) + list(net.conv_after_body.parameters())
-        if self.upsampler == "pixelshuffle":
-            tail += (list(net.conv_before_upsample.parameters()) + list(net.upsample.parameters()) +
-                     list(net.conv_last.parameters()))
-        elif self.upsampler == "nearest+conv":
-            tail += [p for m in (net.conv_before_upsample, net.conv_up1, net.conv_up2, net.conv_hr, net.conv_last)
-                     for p in m.parameters()]
-        elif self.upsampler in (None, ""):
-            tail += list(net.conv_last.parameters())
-        else:
-            tail += list(net.upsample.parameters())
+        tail = list(net.norm.parameters()) + list(net.conv_after_body.parameters()) + self.tail.params(net)
         segs = [tail]
         for gi in range(len(net.layers) - 1, 0, -1):
             segs.append(list(net.layers[gi].parameters()))
@@ -375,16 +333,18 @@ class SwinIREngine(EngineBase):
 
     # ------------------------------------------------------------------------------------
     def convs(self):
-        cs = [self.conv_first] + [c for _, c in self.rstb] + [self.cab]
-        if self.upsampler == "pixelshuffle":
-            cs += [self.cbu] + self.ups + [self.last]
-        elif self.upsampler == "nearest+conv":
-            cs += [self.cbu] + self.nup + [self.hrc, self.last]
-        elif self.upsampler in (None, ""):
-            cs += [self.last]
-        else:
-            cs += [self.up1]
-        return cs
+        return [self.conv_first] + self._resis() + self.tail.convs()
+
+    def _resis(self):
+        """The residual-connection convs: one per RSTB, then conv_after_body."""
+        return [c for _, c in self.rstb] + [self.cab]
+
+    def _wr_ok(self, flag, split, B, h, w, C, N):
+        """Whether a C -> N conv packed for it (flag: its wr / wr_pair / wr_n64) runs on the register-streamed-weight
+        kernel at B x h x w pixels: the kernel tiles the shape (split: kair_conv3x3_wr's argument, "x3": the fp16-pair
+        form) and the batch gives it conv_wr_min_tiles 96-pixel tiles (read per call: set after construction)."""
+        tile = H.conv3x3_wr_x3_tile if split == "x3" else (lambda *shape: H.conv3x3_wr_tile(split, *shape))
+        return bool(flag and self.conv_wr and tile(B, h, w, C, N) > 0 and B * h * w // 96 >= self.conv_wr_min_tiles)
 
     def pack_jobs(self):
         return super().pack_jobs() + [j for b in self.blocks for l in b.linears() for j in l.pack_jobs()]
@@ -428,28 +388,9 @@ class SwinIREngine(EngineBase):
             P["rstb_out"] = [P["rstb_out"][i % len(P["rstb_out"])] for i in range(len(self.rstb))]
         P["nf"], P["n_mean"], P["n_rstd"] = e(M, Cp), e(M), e(M)
         P["fb"] = e(M, Cp)
-        if self.upsampler == "pixelshuffle":
-            nf = 64
-            # split_act: [hi | lo] pair rows (ld 2 nf); the backward reads the hi half as its bf16 operand
-            tl = P["tail_ld"] = 2 * nf if self.split_act else nf
-            P["a0"] = e(M, tl, dt=T)
-            acts, hw = [], M
-            for r in self.ups_r:
-                hw *= r * r
-                acts.append(e(hw, tl, dt=T))
-            P["ups_act"] = acts
-            P["M_hr"] = hw
-            if self.last_narrow_x3:
-                P["narrow_fws"] = e(H.conv3x3_narrow_x3_ws())
-        elif self.upsampler == "nearest+conv":
-            nf = 64
-            P["a0"] = e(M, nf, dt=T)
-            P["nup_act"] = [e(4 * M, nf, dt=T), e(16 * M, nf, dt=T)]
-            P["nhr"] = e(16 * M, nf, dt=T)
-            P["M_hr"] = 16 * M
+        self.tail.plan_forward(self, P, e)
         # '3conv' bottleneck activations (post-LeakyReLU, compute dtype) of every residual connection
-        P["r3"] = {id(r): (e(M, r.Cq, dt=T), e(M, r.Cq, dt=T)) for r in [c for _, c in self.rstb] + [self.cab]
-                   if isinstance(r, _Resi3)}
+        P["r3"] = {id(r): (e(M, r.Cq, dt=T), e(M, r.Cq, dt=T)) for r in self._resis() if isinstance(r, _Resi3)}
         P["E"] = e(B, self.in_ch, Hh * self.scale, Ww * self.scale)
         P["infer"] = infer
         if infer:
@@ -493,32 +434,9 @@ class SwinIREngine(EngineBase):
         P["loss"] = e(1)
         P["loss_ws"] = e(1024)
         P["colsum_ws"] = e(1024 * 256)
-        if self.upsampler == "pixelshuffle":
-            # the HR-image gradient rows: 4 fp32 slots when only the fp32x3 narrow kernels read them (conv_last at
-            # an HR width % 64 == 0), else the 16 slots of the implicit-GEMM conv_last's K = 9 x 16
-            P["dE_ld"] = 4 if self.last_narrow_x3 and (Ww * self.scale) % 64 == 0 else 16
-            P["dE"] = e(P["M_hr"], P["dE_ld"], dt=T)
-            if self.last.narrow or self.last_narrow_x3:
-                P["narrow_ws"] = e(H.conv3x3_narrow_wgrad_ws(self.in_ch))
-                P["narrow_dws"] = e(H.conv3x3_narrow_x3_ws() if self.x3 else H.conv3x3_narrow_dgrad_ws())
-            dpre, hw = [], M
-            for c in self.ups:
-                dpre.append(e(hw, c.Co, dt=T))
-                hw *= c.Co // 64
-            P["dpre"] = dpre
-            P["da0"] = e(M, 64, dt=T)
-        elif self.upsampler == "nearest+conv":
-            nf = 64
-            P["dE"] = e(16 * M, 16, dt=T)
-            P["dz_hr"], P["dz_u"] = e(16 * M, nf, dt=T), e(16 * M, nf, dt=T)
-            P["G_hi"], P["G_lo"] = e(16 * M, nf), e(4 * M, nf)
-            P["da0"] = e(M, nf, dt=T)
-        elif self.upsampler in (None, ""):
-            P["dE"] = e(M, 16, dt=T)
-        else:
-            P["dE"] = e(M, self.up1.Cop, dt=T)
+        self.tail.plan_backward(self, P, e)
         if P["r3"]:
-            q = max(r.Cq for r in [c for _, c in self.rstb] + [self.cab] if isinstance(r, _Resi3))
+            q = max(r.Cq for r in self._resis() if isinstance(r, _Resi3))
             P["r3_dz"] = (e(M, q, dt=T), e(M, q, dt=T))
         P["dfb"] = e(M, Cp)
         if self.conv_tap:
@@ -527,18 +445,16 @@ class SwinIREngine(EngineBase):
             P["conv_halo"] = H.conv_halo_geometry(Hh, Ww, Cp, M, Cp)
             # the register-streamed-weight conv: one 96-pixel tile per workgroup per CU round, so only with
             # at least a full round of tiles (B = 32: 768 tiles; B = 4: 96 -> the halo kernel's N tiles)
-            P["conv_wr"] = bool(self.conv_wr and H.conv3x3_wr_tile(1, B, Hh, Ww, Cp, Cp) > 0 and
-                                H.conv3x3_wr_tile(0, B, Hh, Ww, Cp, Cp) > 0 and M // 96 >= self.conv_wr_min_tiles)
+            P["conv_wr"] = self._wr_ok(True, 1, B, Hh, Ww, Cp, Cp) and self._wr_ok(True, 0, B, Hh, Ww, Cp, Cp)
             if P["conv_wr"]:
                 P["conv_halo"] = True   # the wr kernel leaves the same bf16 copies
             P["conv_bf"] = {}
-            for r in [c for _, c in self.rstb] + [self.cab]:
+            for r in self._resis():
                 if not isinstance(r, _Resi3):
                     P["conv_bf"][id(r)] = (torch.zeros(M, Cp, device=dev, dtype=T), torch.zeros(M, Cp, device=dev, dtype=T))
                     P["conv_bf"][id(r)][1][:, self.C] = 1.0
         if self.x3:   # kair_conv3x3_wr_x3 under the same rule (the x3 NT ring otherwise)
-            P["conv_wr"] = bool(self.conv_wr and H.conv3x3_wr_x3_tile(B, Hh, Ww, Cp, Cp) > 0 and
-                                M // 96 >= self.conv_wr_min_tiles)
+            P["conv_wr"] = self._wr_ok(True, "x3", B, Hh, Ww, Cp, Cp)
         # one shared wgrad workspace sized for the largest (splits * N * K)
         P["wg_ws"] = e(self._max_wgrad_ws(M, P))
         P["wg_ws2"] = (e(P["wg_ws"].numel() * max(1, -self.side_ctas)) if self.grouped_wgrad or self.side_stream
@@ -560,21 +476,7 @@ class SwinIREngine(EngineBase):
                 out += [(M, Cp, Hdp), (M, Hdp, Cp), (M, Cp, nh * self.hp), (M, 3 * nh * self.hp, Cp)]
             out += resi(conv)
         out += resi(self.cab)
-        if self.upsampler == "nearest+conv":
-            out += [(M, 64, 9 * Cp), (4 * M, 64, 9 * 64), (16 * M, 64, 9 * 64), (16 * M, 64, 9 * 64),
-                    (16 * M, 16, 9 * 64)]
-        elif self.upsampler in (None, ""):
-            out.append((M, 16, 9 * Cp))
-        elif self.upsampler == "pixelshuffle":
-            out.append((M, 64, 9 * Cp))
-            hw = M
-            for c in self.ups:
-                out.append((hw, c.Co, 9 * 64))
-                hw *= c.Co // 64
-            out.append((hw, 16, 9 * 64))
-        else:
-            out.append((M, self.up1.Cop, 9 * Cp))
-        return out
+        return out + self.tail.wgrad_shapes(self, M)
 
     def _max_wgrad_ws(self, M, P):
         ws = max(H.wgrad_splits(m, n, k) * n * k for m, n, k in self._wgrad_shapes(M, P))
@@ -625,7 +527,7 @@ class SwinIREngine(EngineBase):
         n = self.norm
         H.layernorm_fwd(cur, Cp, P["nf"], Cp, n.weight, n.bias, P["n_mean"], P["n_rstd"], M, self.C, n.eps)
         self._resi_fwd(self.cab, P, P["nf"], P["fb"], P["f0"])
-        return self._forward_tail(P)
+        return self.tail.forward(self, P)
 
     def _resi_fwd(self, r, P, src, out, resid):
         """out = resi_conv(src) + resid (fp32 token rows, Cp columns)."""
@@ -720,76 +622,6 @@ class SwinIREngine(EngineBase):
             H.gemm_nt(A, B, E, M, N, K, H.X3)
             return
         H.gemm_nt(A, B, E, M, N, K, cd)
-
-    def _forward_tail(self, P):
-        """Reconstruction tail: P['fb'] (conv_after_body + residual) -> P['E']."""
-        cd, Cp, M, B, Hh, Ww = self.cd, self.Cp, P["M"], P["B"], P["H"], P["W"]
-        sa = self.split_act
-        if self.upsampler == "pixelshuffle":
-            tl = P["tail_ld"]
-            lo = (lambda t: t[:, 64:]) if sa else (lambda t: None)   # the lo half of a pair buffer
-            c = self.cbu
-            if (c.wr_n64 and self.conv_wr and H.conv3x3_wr_tile(1, B, Hh, Ww, Cp, 64) > 0 and
-                    M // 96 >= self.conv_wr_min_tiles):
-                H.conv3x3_wr(P["fb"], Cp, 0, c.Wc15, c.bp, None, P["a0"], B, Hh, Ww, Cp, 64, ldo=tl, split=True,
-                             out_lo=lo(P["a0"]), act=H.ACT_LEAKY, slope=0.01)
-            else:
-                self._nt(self._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(),
-                          H.epilogue(P["a0"], ldo=tl, bias=c.bp, act=H.ACT_LEAKY, slope=0.01, out_lo=lo(P["a0"])), M, 64,
-                          9 * Cp, cd)
-            src, h, w = P["a0"], Hh, Ww
-            for c, r, dst in zip(self.ups, self.ups_r, P["ups_act"]):
-                if (c.wr_pair and self.conv_wr and H.conv3x3_wr_tile(1, B, h, w, 64, c.Co) > 0 and
-                        B * h * w // 96 >= self.conv_wr_min_tiles):   # kair_conv3x3_wr, pair form
-                    H.conv3x3_wr(src, tl, 0, c.Wp15, c.bp, None, dst, B, h, w, 64, c.Co, ldo=tl, split=True,
-                                 out_lo=lo(dst), ps_r=r)
-                    src, h, w = dst, h * r, w * r
-                    continue
-                A = H.asplit(H.im2col(src, h, w, c.fcip), pair=True) if sa else H.im2col(src, h, w, 64)
-                self._nt(A, c.fwd(), H.epilogue(dst, mode=H.OUT_PSHUF_SPM, ldo=tl, bias=c.bp, ps=(r, h, w), out_lo=lo(dst)),
-                          B * h * w, c.Co, 9 * c.fcip, cd)
-                src, h, w = dst, h * r, w * r
-            c = self.last
-            if self.last_narrow_x3 and w % 64 == 0:
-                H.conv3x3_narrow_fwd_x3(src, tl, self.X3_AEXP, c.w.detach(), c.bp, self.in_ch, P["narrow_fws"], self.mean,
-                                        self.img_range, None, P["E"], B, h, w)
-                return P["E"]
-            if c.narrow and w % 64 == 0:   # 64 -> in_ch: the narrow-output kernel (weights in VGPRs)
-                H.conv3x3_narrow_fwd(src, tl, 64 if sa else 0, c.Wn, c.bp, self.in_ch, self.mean, self.img_range, None,
-                                     P["E"], B, h, w)
-                return P["E"]
-            self._nt(self._ain(H.im2col(src, h, w, 64, ld=tl), lo(src)), c.fwd(),
-                      H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(self.mean, self.img_range, self.in_ch, h, w)),
-                      B * h * w, c.Cop, 9 * 64, cd)
-        elif self.upsampler == "nearest+conv":
-            c = self.cbu
-            self._nt(H.im2col(P["fb"], Hh, Ww, Cp), c.fwd(),
-                      H.epilogue(P["a0"], bias=c.bp, act=H.ACT_LEAKY, slope=0.01), M, 64, 9 * Cp, cd)
-            src, h, w = P["a0"], Hh, Ww
-            for c, dst in zip(self.nup, P["nup_act"]):   # lrelu(conv(nearest x2)): im2col reads through the upsample
-                h, w = 2 * h, 2 * w
-                self._nt(H.im2col(src, h, w, 64, up=2), c.fwd(), H.epilogue(dst, bias=c.bp, act=H.ACT_LEAKY, slope=0.2),
-                          B * h * w, 64, 9 * 64, cd)
-                src = dst
-            c = self.hrc
-            self._nt(H.im2col(src, h, w, 64), c.fwd(), H.epilogue(P["nhr"], bias=c.bp, act=H.ACT_LEAKY, slope=0.2),
-                      B * h * w, 64, 9 * 64, cd)
-            c = self.last
-            self._nt(H.im2col(P["nhr"], h, w, 64), c.fwd(),
-                      H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(self.mean, self.img_range, self.in_ch, h, w)),
-                      B * h * w, c.Cop, 9 * 64, cd)
-        elif self.upsampler in (None, ""):
-            # x/range + mean with x = (x_in - mean) * range + conv_last(res)  ==  x_in + conv_last(res) / range
-            c = self.last
-            self._nt(self._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(),
-                      H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, resid=P["x"],
-                                 img=(None, self.img_range, self.in_ch, Hh, Ww)), M, c.Cop, 9 * Cp, cd)
-        else:
-            c = self.up1
-            self._nt(self._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(),
-                      H.epilogue(P["E"], mode=H.OUT_PSHUF_NCHW, ldo=0, bias=c.bp, ps=(self.scale, Hh, Ww),
-                                 img=(self.mean, self.img_range, self.in_ch, Hh, Ww)), M, c.Cop, 9 * Cp, cd)
-        return P["E"]
 
     def _block_fwd(self, blk, P, S, x, bi):
         cd = self.cd
@@ -898,12 +730,7 @@ class SwinIREngine(EngineBase):
         # (which also scales the reported loss, undone below)
         wr = loss_weight / self.img_range
         P["e_g"] = self._x3_grad_exp(B * self.in_ch * Hh * self.scale * Ww * self.scale, wr)
-        if self.upsampler == "pixelshuffledirect":
-            H.l1_loss(P["E"], H_img, P["loss"], P["dE"], self.up1.Cop, wr, B, self.in_ch, Hh * self.scale,
-                      Ww * self.scale, P["loss_ws"], ps_r=self.scale, charb_eps=charb_eps)
-        else:
-            H.l1_loss(P["E"], H_img, P["loss"], P["dE"], P.get("dE_ld", 16), wr, B, self.in_ch, Hh * self.scale,
-                      Ww * self.scale, P["loss_ws"], charb_eps=charb_eps)
+        self.tail.loss(self, P, H_img, wr, charb_eps)
         if self.img_range != 1.0:
             P["loss"].mul_(self.img_range)
         self.backward(grads, P)
@@ -913,93 +740,17 @@ class SwinIREngine(EngineBase):
         """Backward given dL/dE (NCHW fp32), for the generic autograd path.  e_off: fp32x3 gradient-exponent shift
         (the range guard's retry, SwinIRFunction.backward)."""
         P = self.cur
-        B, Hh, Ww = P["B"], P["H"], P["W"]
-        # dE = gE through the same layout the loss kernel writes: reuse l1 machinery is not possible,
-        # so scatter with the image->nhwc kernel (channel stride / pre-shuffle layout).
         inv = 1.0 / self.img_range   # E = v / img_range + ...
         if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
             P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()) * inv) + e_off
-        if self.upsampler != "pixelshuffledirect":
-            H.image_to_nhwc(gE.contiguous(), P["dE"], P.get("dE_ld", 16), None, inv, B, self.in_ch, Hh * self.scale,
-                            Ww * self.scale)
-        else:
-            tmp = torch.nn.functional.pixel_unshuffle(gE.contiguous(), self.scale)   # [B, C*r*r, H, W]
-            H.image_to_nhwc(tmp.contiguous(), P["dE"], self.up1.Cop, None, inv, B, tmp.shape[1], Hh, Ww)
+        self.tail.scatter_grad(self, P, gE, inv)
         self.backward(grads, P)
 
     def backward(self, grads, P):
-        cd = self.cd
         self._ax = P["e_g"]   # fp32x3: backward GEMM A operands / fp16 outputs are data gradients
-        B, Hh, Ww, M = P["B"], P["H"], P["W"], P["M"]
-        Cp = self.Cp
+        Hh, Ww, M, Cp = P["H"], P["W"], P["M"], self.Cp
         g = lambda p: grads[p]
-        # ---- reconstruction tail -------------------------------------------------------
-        if self.upsampler == "pixelshuffle":
-            h, w = Hh, Ww
-            for r in self.ups_r:
-                h, w = h * r, w * r
-            c = self.last
-            src = P["ups_act"][-1]
-            tl = P["tail_ld"]   # the activations' row stride (a [hi | lo] pair under split_act: the hi half is read)
-            # conv_last: dgrad into the pre-shuffle layout of the last upsampling conv
-            r_last = self.ups_r[-1]
-            if self.last_narrow_x3 and w % 64 == 0:
-                H.conv3x3_narrow_dgrad_x3(P["dE"], P["dE_ld"], P["e_g"], c.w.detach(), self.in_ch, P["narrow_dws"], P["dpre"][-1],
-                                          self.ups[-1].Co, r_last, B, h, w)
-                H.conv3x3_narrow_wgrad_x3(P["dE"], P["dE_ld"], P["e_g"], src, tl, self.X3_AEXP, self.in_ch, P["narrow_ws"], g(c.w),
-                                          g(c.b), B, h, w)
-            elif c.narrow and w % 64 == 0:   # the narrow-output kernels (rolling row window, fp32 master weight)
-                H.conv3x3_narrow_dgrad(P["dE"], 16, c.w.detach(), self.in_ch, P["narrow_dws"], P["dpre"][-1], self.ups[-1].Co,
-                                       r_last, B, h, w)
-                H.conv3x3_narrow_wgrad(P["dE"], 16, src, tl, self.in_ch, P["narrow_ws"], g(c.w), g(c.b), B, h, w)
-            else:
-                self._nt(H.im2col(P["dE"], h, w, 16, flip=True), H.rows(c.Wd),
-                          H.epilogue(P["dpre"][-1], mode=H.OUT_PUNSHUF_SPM, ldo=self.ups[-1].Co,
-                                     ps=(r_last, h // r_last, w // r_last)),
-                          B * h * w, 64, 9 * 16, cd)
-                self._wgrad(P, H.rows(P["dE"]), H.im2col(src, h, w, 64, ld=tl), B * h * w, 16, 9 * 64, c.map, g(c.w))
-                self._bias_colsum(P, H.rows(P["dE"]), B * h * w, 16, c.mapb, g(c.b))
-            # upsampling convs, last to first
-            for i in range(len(self.ups) - 1, -1, -1):
-                c, r = self.ups[i], self.ups_r[i]
-                h, w = h // r, w // r
-                dpre = P["dpre"][i]
-                src = P["ups_act"][i - 1] if i > 0 else P["a0"]
-                wr_d = (c.wr_pair and self.conv_wr and H.conv3x3_wr_tile(0, B, h, w, c.Co, 64) > 0 and
-                        B * h * w // 96 >= self.conv_wr_min_tiles)
-                if wr_d and i > 0:   # kair_conv3x3_wr: PixelUnshuffle store into the previous conv's pre-shuffle rows
-                    rp = self.ups_r[i - 1]
-                    H.conv3x3_wr(dpre, c.Co, 1, c.Wp16, None, None, P["dpre"][i - 1], B, h, w, c.Co, 64,
-                                 ldo=self.ups[i - 1].Co, split=False, ps_r=-rp)
-                elif wr_d:           # ... or the LeakyReLU'(a0) gate of conv_before_upsample's output
-                    H.conv3x3_wr(dpre, c.Co, 1, c.Wp16, None, None, P["da0"], B, h, w, c.Co, 64, split=False,
-                                 gate=P["a0"], ldg=tl, slope=0.01)
-                elif i > 0:
-                    rp = self.ups_r[i - 1]
-                    self._nt(H.im2col(dpre, h, w, c.Co, flip=True), H.rows(c.Wd),
-                              H.epilogue(P["dpre"][i - 1], mode=H.OUT_PUNSHUF_SPM, ldo=self.ups[i - 1].Co,
-                                         ps=(rp, h // rp, w // rp)),
-                              B * h * w, 64, 9 * c.Co, cd)
-                else:
-                    self._nt(H.im2col(dpre, h, w, c.Co, flip=True), H.rows(c.Wd),
-                              H.epilogue(P["da0"], gate=P["a0"], ldg=tl, gate_kind=2, slope=0.01), M, 64, 9 * c.Co, cd)
-                self._wgrad(P, H.rows(dpre), H.im2col(src, h, w, 64, ld=tl), B * h * w, c.Co, 9 * 64, c.map, g(c.w))
-                self._bias_colsum(P, H.rows(dpre), B * h * w, c.Co, c.mapb, g(c.b))
-            c = self.cbu
-            if (c.wr_n64 and self.conv_wr and H.conv3x3_wr_tile(0, B, Hh, Ww, 64, Cp) > 0 and
-                    M // 96 >= self.conv_wr_min_tiles):
-                H.conv3x3_wr(P["da0"], 64, 1, c.Wc16, None, None, P["dfb"], B, Hh, Ww, 64, Cp, split=False)
-            else:
-                self._nt(H.im2col(P["da0"], Hh, Ww, 64, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * 64, cd)
-            self._wgrad(P, H.rows(P["da0"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=self.C), M, 64, 9 * Cp, c.map,
-                        g(c.w), g(c.b), self.C)
-        elif self.upsampler == "nearest+conv":
-            self._nearest_tail_bwd(P, grads)
-        else:   # pixelshuffledirect (one conv + PixelShuffle) or the denoising conv_last (E = x + conv_last / range)
-            c = self.up1 if self.upsampler == "pixelshuffledirect" else self.last
-            self._nt(H.im2col(P["dE"], Hh, Ww, c.Cop, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * c.Cop, cd)
-            self._wgrad(P, H.rows(P["dE"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=self.C), M, c.Cop, 9 * Cp, c.map,
-                        g(c.w), g(c.b), self.C)
+        self.tail.backward(self, P, grads)   # ---- reconstruction tail: P["dE"] -> P["dfb"]
         # ---- conv_after_body (fb = cab(nf) + f0) ------------------------------------------
         G, D = P["G"], P["D"]
         job = self._resi_bwd(self.cab, P, P["dfb"], P["nf"], D, grads)
@@ -1066,46 +817,6 @@ class SwinIREngine(EngineBase):
         c = self.conv_first
         self._wgrad(P, H.rows(P["dfb"]), H.im2col(P["xin"], Hh, Ww, self.Cin_p, ones_col=self.in_ch), M, Cp,
                     9 * self.Cin_p, c.map, g(c.w), g(c.b), self.in_ch)
-
-    def _nearest_tail_bwd(self, P, grads):
-        """'nearest+conv' reconstruction backward (network_swinir.py:824-830): conv_last, conv_hr and the
-        two conv(nearest x2) stages, each input gradient gated by LeakyReLU' in the dgrad epilogue (conv_hr,
-        conv_up2) or after the 2x2 sum-pool that is nearest x2's adjoint (conv_up2 -> up1 -> cbu);
-        ends with P['dfb'] = dL/d fb."""
-        cd, B, Hh, Ww, M, Cp = self.cd, P["B"], P["H"], P["W"], P["M"], self.Cp
-        g = lambda p: grads[p]
-        h, w = 4 * Hh, 4 * Ww
-        ML = B * h * w
-        c = self.last
-        self._nt(H.im2col(P["dE"], h, w, 16, flip=True), H.rows(c.Wd),
-                  H.epilogue(P["dz_hr"], gate=P["nhr"], gate_kind=2, slope=0.2), ML, 64, 9 * 16, cd)
-        self._wgrad(P, H.rows(P["dE"]), H.im2col(P["nhr"], h, w, 64), ML, 16, 9 * 64, c.map, g(c.w))
-        self._bias_colsum(P, H.rows(P["dE"]), ML, 16, c.mapb, g(c.b))
-        c = self.hrc
-        self._nt(H.im2col(P["dz_hr"], h, w, 64, flip=True), H.rows(c.Wd),
-                  H.epilogue(P["dz_u"], gate=P["nup_act"][1], gate_kind=2, slope=0.2), ML, 64, 9 * 64, cd)
-        self._wgrad(P, H.rows(P["dz_hr"]), H.im2col(P["nup_act"][1], h, w, 64), ML, 64, 9 * 64, c.map, g(c.w))
-        self._bias_colsum(P, H.rows(P["dz_hr"]), ML, 64, c.mapb, g(c.b))
-        dz = P["dz_u"]
-        for i in (1, 0):   # conv_up2 then conv_up1: dz = dL/d(pre-activation) on the (h, w) grid
-            c = self.nup[i]
-            Mi = B * h * w
-            src = P["nup_act"][0] if i == 1 else P["a0"]
-            G_hi = P["G_hi"][:Mi]
-            self._nt(H.im2col(dz, h, w, 64, flip=True), H.rows(c.Wd), H.epilogue(G_hi), Mi, 64, 9 * 64, cd)
-            self._wgrad(P, H.rows(dz), H.im2col(src, h, w, 64, up=2), Mi, 64, 9 * 64, c.map, g(c.w))
-            self._bias_colsum(P, H.rows(dz), Mi, 64, c.mapb, g(c.b))
-            h, w = h // 2, w // 2
-            Mo = B * h * w
-            G_lo = P["G_lo"][:Mo]
-            H.sumpool2x(G_hi, 64, G_lo, 64, B, h, w, 64)
-            nxt = P["dz_hr"][:Mo] if i == 1 else P["da0"]      # dz_hr is free again after conv_hr's wgrad
-            H.act_grad_cast(G_lo, 64, src, 64, nxt, 64, Mo, 64, 2, 0.2 if i == 1 else 0.01)
-            dz = nxt
-        c = self.cbu
-        self._nt(H.im2col(P["da0"], Hh, Ww, 64, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * 64, cd)
-        self._wgrad(P, H.rows(P["da0"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=self.C), M, 64, 9 * Cp, c.map,
-                    g(c.w), g(c.b), self.C)
 
     def _wg(self, P, A, Bop, N, K, lin, grads, ones_col):
         """One block linear's weight gradient: queued for the RSTB's grouped launch, or issued now."""

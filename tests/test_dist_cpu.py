@@ -94,19 +94,43 @@ def test_gloo_world2_allreduce_and_dp_equivalence():
     torch.testing.assert_close(out[0]["dp_grad"], full, rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.parametrize("ups", ["pixelshuffle", "pixelshuffledirect"])
+# the small network (embed 60, depths [2, 2], img 16) in every tail configuration: (upsampler, scale, channels,
+# resi_connection) -> (len(convs()), len(pack_jobs())) of the bf16 engine before the tails became objects
+SMALL_TAILS = {
+    "pixelshuffle-x2": (("pixelshuffle", 2, 3, "1conv"), (7, 69)),
+    "pixelshuffle-x3": (("pixelshuffle", 3, 3, "1conv"), (7, 69)),
+    "pixelshuffle-x4": (("pixelshuffle", 4, 3, "1conv"), (8, 72)),
+    "pixelshuffledirect-x2": (("pixelshuffledirect", 2, 3, "1conv"), (5, 62)),
+    "nearest+conv-x4": (("nearest+conv", 4, 3, "1conv"), (9, 74)),
+    "None-1ch": ((None, 1, 1, "1conv"), (5, 62)),
+    "empty-3conv": (("", 1, 3, "3conv"), (5, 80)),
+}
+
+
+@pytest.mark.parametrize("ups", ["pixelshuffle", "pixelshuffledirect"] + list(SMALL_TAILS))
 def test_swinir_gradient_segments_tile_the_flat_buffer(ups):
     """The all-reduce buckets the trainer overlaps with backward: the engine's gradient segments are
-    contiguous in parameter order, tile the flat buffer and come last layer first."""
+    contiguous in parameter order, tile the flat buffer and come last layer first.  The layer objects and the weight
+    packs are counted too: the order of convs() is the pack-job order."""
     from kair_amd.engine.swinir_engine import SwinIREngine
     from kair_amd.engine.trainer import segment_buckets
     from kair_amd.models.network_swinir import SwinIR
-    net = SwinIR(upscale=4 if ups == "pixelshuffle" else 2, in_chans=3, img_size=48, window_size=8, img_range=1.0,
-                 depths=[6] * 6, embed_dim=180, num_heads=[6] * 6, mlp_ratio=2, upsampler=ups, resi_connection="1conv")
+    if ups in SMALL_TAILS:
+        (kind, sc, ch, resi), counts = SMALL_TAILS[ups]
+        net = SwinIR(upscale=sc, in_chans=ch, img_size=16, window_size=8, img_range=1.0, depths=[2, 2], embed_dim=60,
+                     num_heads=[6, 6], mlp_ratio=2, upsampler=kind, resi_connection=resi)
+    else:
+        counts = {"pixelshuffle": (12, 488), "pixelshuffledirect": (9, 472)}[ups]
+        net = SwinIR(upscale=4 if ups == "pixelshuffle" else 2, in_chans=3, img_size=48, window_size=8, img_range=1.0,
+                     depths=[6] * 6, embed_dim=180, num_heads=[6] * 6, mlp_ratio=2, upsampler=ups, resi_connection="1conv")
     eng = SwinIREngine(net, "bf16")
     params = list(net.parameters())
     b = segment_buckets(params, eng.grad_segments())
-    assert b is not None and len(b) == 7
+    assert b is not None and len(b) == len(net.layers) + 1
     assert b[0][1] == sum(p.numel() for p in params)      # the tail bucket ends the buffer
     assert [lo for lo, _ in b] == sorted([lo for lo, _ in b], reverse=True)
     assert b[-1][0] == 0
+    assert (len(eng.convs()), len(eng.pack_jobs())) == counts
+    net.upsampler = "bicubic"
+    with pytest.raises(NotImplementedError, match="bicubic"):
+        SwinIREngine(net, "bf16")

@@ -117,3 +117,20 @@ def test_defined_once_under_engine(pattern):
             with open(os.path.join(d, f)) as fh:
                 hits += [f] * len(re.findall(pattern, fh.read()))
     assert hits == ["base.py"], hits
+
+
+def test_swinir_tail_and_conv_wr_rule_single_sourced():
+    """The SwinIR engine neither branches on the upsampler (swinir_tail.py's classes do) nor reads the environment, and
+    the register-streamed conv's eligibility rule is written in one function of the engine package."""
+    d = os.path.join(ROOT, "kair_amd", "engine")
+    with open(os.path.join(d, "swinir_engine.py")) as fh:
+        src = fh.read()
+    assert "self.upsampler ==" not in src and "os.environ" not in src
+    callers = []
+    for f in sorted(os.listdir(d)):
+        if f.endswith(".py"):
+            with open(os.path.join(d, f)) as fh:
+                for fn in re.split(r"\n(?= *def )", fh.read()):   # one piece per function (nested ones included)
+                    if "conv3x3_wr_tile(" in fn:
+                        callers.append((f, re.match(r" *def (\w+)", fn).group(1)))
+    assert callers == [("swinir_engine.py", "_wr_ok")], callers

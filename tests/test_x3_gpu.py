@@ -17,6 +17,7 @@ if not torch.cuda.is_available():
 
 from conftest import load_golden, sub_grads, sub_state  # noqa: E402
 from kair_amd import _hip as H  # noqa: E402
+from kair_amd.engine.swinir_engine import SwinIREngine  # noqa: E402
 from kair_amd.engine.trainer import FusedTrainer  # noqa: E402
 from kair_amd.models.network_swinir import SwinIR  # noqa: E402
 from oracle import image as oimg  # noqa: E402
@@ -609,11 +610,10 @@ def test_swinir_classical_full_x3_vs_oracle():
     assert worst[0] < 1e-3, worst
 
 
-def test_swinir_x3_lnfuse_engine(monkeypatch):
-    """The opt-in fused LayerNorm backward (KAIR_X3_LNFUSE=1: kair_gemm_nt_x3_lnbwd at both LayerNorms of every Swin
+def test_swinir_x3_lnfuse_engine():
+    """The opt-in fused LayerNorm backward (x3_lnfuse=True: kair_gemm_nt_x3_lnbwd at both LayerNorms of every Swin
     block) against the CPU oracle at the fp32 bars: 2 RSTBs of embed 180 (the one-tile C <= 192 the fused epilogue
     needs), output and every gradient."""
-    monkeypatch.setenv("KAIR_X3_LNFUSE", "1")
     torch.manual_seed(5)
     kw = dict(upscale=2, in_chans=3, img_size=16, window_size=8, img_range=1.0, depths=[2, 2], embed_dim=180,
               num_heads=[6, 6], mlp_ratio=2, upsampler="pixelshuffle", resi_connection="1conv")
@@ -625,6 +625,7 @@ def test_swinir_x3_lnfuse_engine(monkeypatch):
     Er = ref(L)
     torch.nn.functional.l1_loss(Er, Hh).backward()
     net = net.to(dev).train()
+    net._engine = SwinIREngine(net, "fp32x3", x3_lnfuse=True)
     assert net.engine().x3_lnfuse
     E = net(L.to(dev))
     torch.nn.functional.l1_loss(E, Hh.to(dev)).backward()

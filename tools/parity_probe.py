@@ -89,9 +89,9 @@ def main():
         P16 = e16.cur
         fb16 = P16["fb"].clone()
         P16["fb"].copy_(fb32)
-        report("bf16 tail on fp32 body", e16._forward_tail(P16).float().cpu())
+        report("bf16 tail on fp32 body", e16.tail.forward(e16, P16).float().cpu())
         P32["fb"].copy_(fb16)
-        report("fp32 tail on bf16 body", e32._forward_tail(P32).float().cpu())
+        report("fp32 tail on bf16 body", e32.tail.forward(e32, P32).float().cpu())
         print(json.dumps({"fb_rel_rms(bf16 body)": float((fb16 - fb32).pow(2).mean().sqrt() / fb32.pow(2).mean().sqrt())}))
         nu, eu = engine_of("bf16", fused=False)
         report("bf16_engine(unfused blocks)", nu(x).float().cpu())
