@@ -265,7 +265,9 @@ int kair_wgrad_grouped(const kair_wgrad_job* jobs, int njobs, long M, float* ws,
  * kair_wgrad_grouped_ws()). */
 int kair_wgrad_grouped_ex(const kair_wgrad_job* jobs, int njobs, long M, float* ws, int max_ctas, void* stream);
 /* bias_grad[n_ref] (+)= sum_m G[m][n]  for an operand G of width Np (conv biases without a pad
- * column).  ws: 1024 * Np floats. */
+ * column).  ws: kair_colsum_ws(Np) floats, the per-workgroup partial sums the launch writes (every one of
+ * them, whatever M). */
+long kair_colsum_ws(int Np);
 int kair_colsum(const kair_operand* G, long M, int Np, const kair_wmap* map, float* bias_grad,
                 float* ws, int accumulate, void* stream);
 

@@ -120,6 +120,7 @@ _SIGS = {
     "kair_pack_table_build": [ctypes.POINTER(PackJob), c_int, c_vp],
     "kair_pack_weights": [c_vp, c_int, c_long, c_vp],
     "kair_wgrad_finalize": [c_vp, c_int, ctypes.POINTER(WMap), c_vp, c_vp, c_int, c_int, c_vp],
+    "kair_colsum_ws": [c_int],
     "kair_colsum": [ctypes.POINTER(Operand), c_long, c_int, ctypes.POINTER(WMap), c_vp, c_vp, c_int, c_vp],
     "kair_layernorm_fwd": [c_vp, c_long, c_vp, c_int, c_long, c_vp, c_vp, c_vp, c_vp, c_long, c_int, c_float, c_int,
                            c_int, c_int, c_int, c_int, c_vp],
@@ -255,7 +256,7 @@ _SIGS = {
     "kair_last_error": [],
     "kair_device_arch": [ctypes.c_char_p, c_int],
 }
-_RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
+_RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_colsum_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
             "kair_jpeg_workspace_bytes": c_long}
@@ -553,7 +554,20 @@ def wgrad_finalize(partial, splits, m, grad, bias_grad=None, ones_col=-1, accumu
                                     int(accumulate), stream_ptr()), "wgrad_finalize")
 
 
+_COLSUM_WS = {}
+
+
+def colsum_ws(Np):
+    """Workspace floats of a kair_colsum launch over Np columns: every partial sum it writes (cached per Np)."""
+    n = _COLSUM_WS.get(Np)
+    if n is None:
+        n = _COLSUM_WS[Np] = lib().kair_colsum_ws(Np)
+    return n
+
+
 def colsum(G, M, Np, m, bias_grad, ws, accumulate=False):
+    if ws.numel() < colsum_ws(Np):
+        raise ValueError(f"kair_colsum: workspace too small for Np = {Np} ({ws.numel()} < {colsum_ws(Np)} floats)")
     check(lib().kair_colsum(ctypes.byref(G), M, Np, ctypes.byref(m), ptr(bias_grad), ptr(ws), int(accumulate),
                             stream_ptr()), "colsum")
 

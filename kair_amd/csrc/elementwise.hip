@@ -1040,11 +1040,16 @@ extern "C" int kair_row_copy(const float* src, long lds, long M, int C, const ka
   return 0;
 }
 
+// planes of Np partial column sums a kair_colsum launch leaves in its workspace
+constexpr int COLSUM_NB = 512;
+
+extern "C" long kair_colsum_ws(int Np) { return Np > 0 ? (long)COLSUM_NB * Np : 0; }
+
 extern "C" int kair_colsum(const kair_operand* G, long M, int Np, const kair_wmap* map, float* bias_grad, float* ws,
                            int accumulate, void* stream) {
   KAIR_CHECK_ARG(G && G->ptr && map && bias_grad && ws, "colsum: null pointer");
   KAIR_CHECK_ARG(G->mode == KAIR_LD_ROWS && G->win_ws == 0, "colsum: plain row operands only");
-  const int nb = 512;
+  const int nb = COLSUM_NB;
   const long rows_per = (M + nb - 1) / nb;
   dim3 grid(nb, (Np + 255) / 256);
   hipStream_t s = (hipStream_t)stream;

@@ -73,7 +73,7 @@ class DnCNNEngine(ConvEngineBase):
         P["dzf"] = e(M, nc)   # fp32 gradient rows before the compute-dtype cast (bias gradients)
         P["bn_ws"] = e(H.bn_ws(nc))
         P["loss"], P["loss_ws"] = e(1), e(1024)
-        P["colsum_ws"] = e(1024 * 256)
+        P["colsum_ws"] = e(H.colsum_ws(max(c.Cop for c in self.convs())))
         shapes = [(M, c.Cop, 9 * c.Cip) for c, _, _, _ in self.layers]
         P["wg_ws"] = e(self.wgrad_ws_size(shapes))
         return P

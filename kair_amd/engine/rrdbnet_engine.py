@@ -112,7 +112,7 @@ class RRDBNetEngine(ConvEngineBase):
         P["Gd"], P["dz5"], P["dzg"], P["gy"] = e(M, CD), e(M, nf, dt=T), e(M, gc, dt=T), e(M, nf)
         P["dzf"] = e(ML, nf)   # fp32 gradient rows before the compute-dtype cast (bias gradients)
         P["loss"], P["loss_ws"] = e(1), e(1024)
-        P["colsum_ws"] = e(1024 * 256)
+        P["colsum_ws"] = e(H.colsum_ws(max(c.Cop for c in self.convs())))
         shapes = [(M, nf, 9 * self.Cin_p), (M, nf, 9 * nf), (ML, 16, 9 * nf), (ML, nf, 9 * nf)]
         shapes += [(B * hh * ww, nf, 9 * nf) for hh, ww in levels]
         shapes += [(M, c.Cop, 9 * c.Cip) for c in self.rdbs[0]]

@@ -433,7 +433,7 @@ class SwinIREngine(EngineBase):
         P["attn_ws"] = e(H.window_attn_bwd_ws(nWin, nh, self.ws))
         P["loss"] = e(1)
         P["loss_ws"] = e(1024)
-        P["colsum_ws"] = e(1024 * 256)
+        P["colsum_ws"] = e(H.colsum_ws(max(self._colsum_widths())))
         self.tail.plan_backward(self, P, e)
         if P["r3"]:
             q = max(r.Cq for r in self._resis() if isinstance(r, _Resi3))
@@ -717,6 +717,12 @@ class SwinIREngine(EngineBase):
         oc = 4 * Cp + C   # the center tap's channel C: 1.0 for every pixel
         self._wgrad(P, H.rows(gbf), H.im2col(xbf, P["H"], P["W"], Cp, ones_col=oc, ones_in_data=True), M, Cp, 9 * Cp,
                     r.map, gw, gb, oc, ws=ws, max_ctas=max_ctas)
+
+    def _colsum_widths(self):
+        """Np of every _bias_colsum the step can issue: the '3conv' residuals' (Cp and the bottleneck q) and the
+        tail's."""
+        r3 = [r.Cq for r in self._resis() if isinstance(r, _Resi3)]
+        return [self.Cp] + r3 + self.tail.colsum_widths()
 
     def _bias_colsum(self, P, G, M, Np, layer_map, bgrad):
         H.colsum(G, M, Np, layer_map, bgrad, P["colsum_ws"])

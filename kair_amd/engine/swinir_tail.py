@@ -25,6 +25,10 @@ class _Tail:
     def plan_forward(self, eng, P, e):
         pass
 
+    def colsum_widths(self):
+        """Np of every eng._bias_colsum the tail's backward can issue (sizes P['colsum_ws'])."""
+        return []
+
     def loss(self, eng, P, H_img, wr, charb_eps):
         """L1 / Charbonnier loss into P['loss'], its gradient into the P['dE'] rows."""
         H.l1_loss(P["E"], H_img, P["loss"], P["dE"], P.get("dE_ld", 16), wr, P["B"], eng.in_ch, P["H"] * eng.scale,
@@ -93,6 +97,9 @@ class PixelShuffleTail(_Tail):
             out.append((hw, c.Co, 9 * NF))
             hw *= c.Co // NF
         return out + [(hw, 16, 9 * NF)]
+
+    def colsum_widths(self):
+        return [16] + [c.Co for c in self.ups]
 
     def forward(self, eng, P):
         cd, Cp, M, B, Hh, Ww = eng.cd, eng.Cp, P["M"], P["B"], P["H"], P["W"]
@@ -220,6 +227,9 @@ class NearestConvTail(_Tail):
 
     def wgrad_shapes(self, eng, M):
         return [(M, NF, 9 * eng.Cp), (4 * M, NF, 9 * NF), (16 * M, NF, 9 * NF), (16 * M, NF, 9 * NF), (16 * M, 16, 9 * NF)]
+
+    def colsum_widths(self):
+        return [self.last.Cop, self.hrc.Cop, NF]
 
     def forward(self, eng, P):
         cd, Cp, M, B, h, w = eng.cd, eng.Cp, P["M"], P["B"], P["H"], P["W"]

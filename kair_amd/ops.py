@@ -61,7 +61,7 @@ def _wgrad(A, Bop, M, Np, Kp, wmap, grad, compute):
 
 
 def _colsum(G, M, Np, N, grad):
-    ws = torch.empty(1024 * Np, device=grad.device)
+    ws = torch.empty(H.colsum_ws(Np), device=grad.device)
     H.colsum(H.rows(G), M, Np, H.wmap(4, N, 0, (1, N, Np), (1, 1, 1)), grad, ws)
 
 

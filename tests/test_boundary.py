@@ -56,6 +56,17 @@ def test_error_channel_without_gpu():
     assert b"layernorm_fwd" in L.kair_last_error()
 
 
+def test_colsum_workspace_contract_without_gpu():
+    """kair_colsum_ws(Np) is the host-side size of what a kair_colsum launch writes (512 planes of Np floats), and
+    H.colsum refuses a shorter workspace before it touches an operand: the 1024 x 256 floats the engines once
+    allocated hold the x3 upsampling conv's 576 columns no longer."""
+    from kair_amd import _hip
+    assert [_hip.colsum_ws(n) for n in (16, 256, 512, 576)] == [512 * 16, 512 * 256, 512 * 512, 512 * 576]
+    assert _hip.colsum_ws(576) > 1024 * 256 >= _hip.colsum_ws(512)
+    with pytest.raises(ValueError):
+        _hip.colsum(None, 1, 576, None, None, torch.empty(1024 * 256))
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "kair_amd")
     offenders = []

@@ -170,21 +170,39 @@ def test_conv3x3_split_weights(shape):
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("M,Np,ld", [(100003, 16, 16), (70000, 256, 256), (4097, 64, 72), (5000, 20, 20)])
+@pytest.mark.parametrize("M,Np,ld", [(100003, 16, 16), (70000, 256, 256), (4097, 64, 72), (5000, 20, 20),
+                                     # three column blocks of the scalar kernel (the x3 upsampling conv's width)
+                                     (4097, 576, 576),
+                                     (3, 576, 576),        # fewer rows than partial planes: empty planes
+                                     (1500, 520, 528),     # last column block partial
+                                     (700, 264, 264),      # Np % 8 == 0 above 256: not the vector kernel's
+                                     (2000, 256, 264), (2000, 248, 256)])   # vector kernel, widest and one short
 def test_colsum_bias_gradient(dt, M, Np, ld):
     """Bias gradient = column sums of the output-gradient rows (vectorised and scalar paths),
-    deterministic (two launches agree bit for bit)."""
+    deterministic (two launches agree bit for bit).  The workspace is exactly kair_colsum_ws(Np) floats, the
+    middle third of a buffer whose outer thirds must come back untouched."""
     g = torch.Generator().manual_seed(M)
     x = torch.randn(M, ld, generator=g).to(dt)
     ref = x[:, :Np].double().sum(0)
     m = H.wmap(0, Np, 0)
     out = torch.empty(Np, device=dev)
     out2 = torch.empty(Np, device=dev)
-    ws = torch.empty(512 * max(Np, 256), device=dev)
+    n = H.colsum_ws(Np)
+    assert n == 512 * Np
+    buf = torch.full((3 * n,), 0x5A5AA5A5, dtype=torch.int32, device=dev)
+    ws = buf[n:2 * n].view(torch.float32)
     G = H.rows(x.to(dev))
-    H.colsum(G, M, Np, m, out, ws)
-    H.colsum(G, M, Np, m, out2, ws)
+    vec = Np % 8 == 0 and Np <= 256 and ld % 8 == 0
     torch.cuda.synchronize()
+    H.ktime_begin(8)
+    try:
+        H.colsum(G, M, Np, m, out, ws)
+        H.colsum(G, M, Np, m, out2, ws)
+    finally:
+        nk = H.ktime_end()
+    torch.cuda.synchronize()
+    assert nk == 4 and ("colsum_partial_v" in H.ktime_read(0)[1]) == vec, H.ktime_read(0)[1]
+    assert bool((buf[:n] == 0x5A5AA5A5).all()) and bool((buf[2 * n:] == 0x5A5AA5A5).all())
     assert torch.equal(out, out2)
     assert (out.double().cpu() - ref).abs().max().item() < 1e-3 * (1 + ref.abs().max().item())
 

@@ -1,7 +1,7 @@
 """The narrow-output 3x3 conv kernels (csrc/tail.hip) -- SwinIR's conv_last 64 -> 3 at the HR size
 (network_swinir.py:745, :817) -- against float64 torch autograd of the same conv: forward over a hi/lo
 pair image (split activations, split weights: ~2^-16 relative), input gradient into a row layout and
-into the PixelUnshuffle(2) sub-pixel-major layout of the previous conv, weight + bias gradient
+into the PixelUnshuffle(2) / PixelUnshuffle(3) sub-pixel-major layout of the previous conv, weight + bias gradient
 (deterministic: two launches agree bit for bit)."""
 import pytest
 import torch
@@ -54,9 +54,19 @@ def test_narrow_fwd(NR, shape):
     assert errs[0] < 3e-5 and errs[1] > 8 * errs[0], errs
 
 
-@pytest.mark.parametrize("ps_r", [0, 2])
+def _r3_cases(ps_r):
+    """(B, H, W, NR) of a narrow-dgrad case: PixelUnshuffle(3) needs H, W % 3 == 0 beside W % 64 == 0, so 6 x 192,
+    with NR = 3 and NR = 1."""
+    return [(2, 6, 192, 3), (2, 6, 192, 1)] if ps_r == 3 else [(2, 16, 64, 3)]
+
+
+@pytest.mark.parametrize("ps_r", [0, 2, 3])
 def test_narrow_dgrad(ps_r):
-    B, Hh, Ww, NR = 2, 16, 64, 3
+    for shape in _r3_cases(ps_r):
+        _narrow_dgrad(ps_r, *shape)
+
+
+def _narrow_dgrad(ps_r, B, Hh, Ww, NR):
     g = torch.Generator().manual_seed(9 + ps_r)
     dE = torch.randn(B, NR, Hh, Ww, generator=g).bfloat16().float()
     w = torch.randn(NR, 64, 3, 3, generator=g) * 0.05
@@ -168,9 +178,13 @@ def test_narrow_fwd_x3(NR, shape):
     assert rel_err(out, ref) < 2e-6
 
 
-@pytest.mark.parametrize("ps_r", [0, 2])
+@pytest.mark.parametrize("ps_r", [0, 2, 3])
 def test_narrow_dgrad_x3(ps_r):
-    B, Hh, Ww, NR = 2, 16, 64, 3
+    for shape in _r3_cases(ps_r):
+        _narrow_dgrad_x3(ps_r, *shape)
+
+
+def _narrow_dgrad_x3(ps_r, B, Hh, Ww, NR):
     g = torch.Generator().manual_seed(49 + ps_r)
     dE = torch.randn(B, NR, Hh, Ww, generator=g) * 2.0 ** -12   # a mean-loss gradient's scale, exponent 12 + 4
     w = torch.randn(NR, 64, 3, 3, generator=g) * 0.05

@@ -21,9 +21,7 @@ from kair_amd.engine.swinir_engine import SwinIREngine  # noqa: E402
 from kair_amd.models.network_swinir import SwinIR  # noqa: E402
 
 B = 2
-# pixelshuffle x3 is left out: the bias column sum of its 576-channel upsampling conv writes 512 x 576 partials into
-# P["colsum_ws"] (1024 x 256 floats), past its end -- not to be run until that buffer is sized for it
-TAILS = [("ps_x2", "pixelshuffle", 2, 3, "1conv"),
+TAILS = [("ps_x2", "pixelshuffle", 2, 3, "1conv"), ("ps_x3", "pixelshuffle", 3, 3, "1conv"),
          ("ps_x4", "pixelshuffle", 4, 3, "1conv"), ("direct_x2", "pixelshuffledirect", 2, 3, "1conv"),
          ("nearest_x4", "nearest+conv", 4, 3, "1conv"), ("none_c1", None, 1, 1, "1conv"), ("plain_3conv", "", 1, 3, "3conv")]
 DTYPES = ("bf16", "fp32", "fp32x3")
