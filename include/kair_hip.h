@@ -536,6 +536,15 @@ int kair_image_to_nhwc(const float* img, void* out, int dtype, int ldc, const fl
  * The conv reading it packs its weights tied over both halves (kair_wmap kG*kGr = 2K, kinds 1 / 9). */
 int kair_image_to_nhwc_hilo(const float* img, void* out, int ldc, const float* mean, float img_range,
                             int B, int C, int H, int W, void* stream);
+/* FFDNet's head: PixelUnshuffle(2) of the NCHW fp32 image [B][C][H][W] into NHWC rows (dtype KAIR_F32 / KAIR_BF16,
+ * channel stride ldc, ldc % 8 == 0, out 16-byte aligned) over the half grid Hh = ceil(H/2), Wh = ceil(W/2); row
+ * (b, y, x), channel c*4 + i*2 + j (F.pixel_unshuffle's order).
+ * sigma != NULL (input pack, ldc >= 4C + 1): the value is img[b][c][min(2y+i, H-1)][min(2x+j, W-1)]
+ *   (ReplicationPad2d to even sizes), channel 4C is sigma[b] (the noise level of sample b), channels above it 0.
+ * sigma == NULL (gradient pack, ldc >= 4C): sub-pixels with 2y+i >= H or 2x+j >= W are 0 (the cropped pixels of the
+ *   padded output have no gradient), channels >= 4C are 0: the pre-PixelShuffle(2) rows of an output gradient. */
+int kair_ffd_pack(const float* img, const float* sigma, void* out, int dtype, int ldc, int B, int C, int H, int W,
+                  void* stream);
 /* L1 loss (nn.L1Loss, mean): loss_out[0] = weight*mean|E-H|; grad dE = weight*sign(E-H)/numel written
  * for the last conv's dgrad: NHWC (dtype, channel stride ldc) when ps_r == 1, or in the
  * pre-PixelShuffle(ps_r) layout [b][y/r][x/r][c*r*r + (y%r)*r + x%r] otherwise.  ws: 1024 floats. */
@@ -721,6 +730,12 @@ int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int* params, i
                   unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
 int kair_synth_dn_map(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
                       int PS, unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
+/* kair_synth_dn_level: DatasetFFDNet's train branch (data/dataset_ffdnet.py), kair_synth_dn_map's device code without
+ * the map channel: outL [B][C][PS][PS] is kair_synth_dn_map's outL[:, :C] bit for bit (same params, seed, step), and
+ * the level sigma_b goes to outC[b] ([B] fp32) instead. */
+int kair_synth_dn_level(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
+                        int PS, unsigned long long seed, unsigned long long step, float* outH, float* outL, float* outC,
+                        void* stream);
 
 /* ---- USRNet training data (csrc/synth_usr.hip; DatasetUSRNet.__getitem__, data/dataset_usrnet.py:46-113) --------
  * kair_usr_gauss_kernels: B blur kernels [B][ksize][ksize] fp32, utils_sisr.gen_kernel (utils_sisr.py:172-215) with

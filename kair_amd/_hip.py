@@ -153,6 +153,7 @@ _SIGS = {
                                 c_int, c_vp, c_int, c_int, c_vp],
     "kair_image_to_nhwc": [c_vp, c_vp, c_int, c_int, c_vp, c_float, c_int, c_int, c_int, c_int, c_vp],
     "kair_image_to_nhwc_hilo": [c_vp, c_vp, c_int, c_vp, c_float, c_int, c_int, c_int, c_int, c_vp],
+    "kair_ffd_pack": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "kair_conv3x3_narrow_fwd": [c_vp, c_long, c_int, c_vp, c_vp, c_int, c_vp, c_float, c_vp, c_vp, c_int, c_int, c_int,
                                 c_vp],
     "kair_conv3x3_wr_tile": [c_int, c_int, c_int, c_int, c_int, c_int],
@@ -217,6 +218,8 @@ _SIGS = {
                       c_vp, c_vp, c_vp],
     "kair_synth_dn_map": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.c_ulonglong,
                           ctypes.c_ulonglong, c_vp, c_vp, c_vp],
+    "kair_synth_dn_level": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.c_ulonglong,
+                            ctypes.c_ulonglong, c_vp, c_vp, c_vp, c_vp],
     "kair_usr_gauss_kernels": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp],
     "kair_synth_usr": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
                        c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_int, c_vp],
@@ -788,6 +791,20 @@ def image_to_nhwc(img, out, ldc, mean, img_range, B, C, H, W):
                                    stream_ptr()), "image_to_nhwc")
 
 
+def ffd_pack(img, sigma, out, ldc, B, C, H, W):
+    """FFDNet's PixelUnshuffle(2) head (kair_ffd_pack): img [B, C, H, W] fp32 -> out rows [B * ceil(H/2) * ceil(W/2), ldc]
+    (fp32 / bf16).  sigma [B] fp32: replicate-padded input pack with the level in channel 4C; sigma None: the
+    zero-padded pack of an output gradient."""
+    require_device(img, out, sigma)
+    if img.dtype != torch.float32 or not img.is_contiguous() or tuple(img.shape) != (B, C, H, W):
+        raise ValueError(f"ffd_pack: img must be a contiguous fp32 {(B, C, H, W)}")
+    if sigma is not None and (sigma.dtype != torch.float32 or not sigma.is_contiguous() or sigma.numel() != B):
+        raise ValueError(f"ffd_pack: sigma must be {B} contiguous fp32 levels")
+    if not out.is_contiguous() or out.numel() < B * ((H + 1) // 2) * ((W + 1) // 2) * ldc:
+        raise ValueError("ffd_pack: out is smaller than the packed rows")
+    check(lib().kair_ffd_pack(ptr(img), ptr(sigma), ptr(out), dtype_code(out), ldc, B, C, H, W, stream_ptr()), "ffd_pack")
+
+
 def l1_loss(E, H, loss_out, dE, ldc, weight, B, C, Hh, Ww, ws, ps_r=1, charb_eps=None):
     """L1 (mean) loss + its gradient; charb_eps set: the Charbonnier loss sqrt(d^2 + eps) instead."""
     if charb_eps is not None:
@@ -979,6 +996,25 @@ def synth_dn_map(pool, params, B, PS, seed, step, outH, outL, sigma_col=4):
     pp, ps = _rows_of(params, torch.int32, max(5, sigma_col + 1), "synth_dn_map params")
     check(lib().kair_synth_dn_map(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
                                   stream_ptr()), "synth_dn_map")
+
+
+def synth_dn_level(pool, params, B, PS, seed, step, outH, outL, outC, sigma_col=4):
+    """FFDNet batch (kair_synth_dn_level): synth_dn_map's parameter rows; outH and outL [B, C, PS, PS] (outL is
+    synth_dn_map's outL[:, :C] bit for bit), the levels sigma / 255 in outC ([B] fp32, any shape of B elements)."""
+    require_device(pool, params, outH, outL, outC)
+    N, C, Hs, Ws = pool.shape
+    if pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise ValueError("synth_dn_level: pool must be contiguous fp32")
+    if params.shape[0] < B:
+        raise ValueError("synth_dn_level: fewer parameter rows than samples")
+    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C, PS, PS))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+            raise ValueError(f"synth_dn_level: output must be a contiguous fp32 {shp}")
+    if outC.dtype != torch.float32 or not outC.is_contiguous() or outC.numel() != B:
+        raise ValueError(f"synth_dn_level: outC must hold {B} contiguous fp32 levels")
+    pp, ps = _rows_of(params, torch.int32, max(5, sigma_col + 1), "synth_dn_level params")
+    check(lib().kair_synth_dn_level(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
+                                    ptr(outC), stream_ptr()), "synth_dn_level")
 
 
 def _rows_of(t, dtype, ncol, what):

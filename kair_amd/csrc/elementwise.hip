@@ -619,6 +619,67 @@ __global__ void image_to_nhwc_hilo_kernel(const float* __restrict__ img, bf16* _
   out[t] = c < half ? hi : (bf16)(v - (float)hi);
 }
 
+// FFDNet's head (kair_ffd_pack): PixelUnshuffle(2) of an NCHW image into NHWC rows over the half grid.  One thread
+// per output pixel: per source channel it reads the 2 x 2 block as two adjacent pairs along x (lane l reads floats
+// 2l, 2l + 1 of a row, so a wavefront covers 128 consecutive floats), and it stores the row's ldc channels 8 at a time
+// (16-byte pieces).  GRAD: out-of-image sub-pixels are 0 (the cropped pixels of the padded output have no gradient)
+// and there is no level channel; otherwise they repeat the last row / column (ReplicationPad2d) and channel 4C is
+// sigma[b].  PAIR: W even and img 8-byte aligned, so every pair is one aligned 8-byte load.
+__device__ __forceinline__ void ffd_store8(float* o, const float* v) {
+  *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
+  *(float4*)(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+__device__ __forceinline__ void ffd_store8(bf16* o, const float* v) {
+  bf16x8 p;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) p[j] = (bf16)v[j];
+  *(bf16x8*)o = p;
+}
+
+template <typename T, bool GRAD, bool PAIR>
+__global__ __launch_bounds__(256) void ffd_pack_kernel(const float* __restrict__ img, const float* __restrict__ sigma,
+                                                       T* __restrict__ out, int ldc, int C, int H, int W, int Hh, int Wh,
+                                                       long npix) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npix) return;
+  const int x = (int)(t % Wh);
+  const long r = t / Wh;
+  const int y = (int)(r % Hh);
+  const long b = r / Hh;
+  const bool hasr = 2 * y + 1 < H, hasc = 2 * x + 1 < W;   // (2y < H and 2x < W always: Hh = ceil(H/2))
+  const long HW = (long)H * W;
+  const float* p0 = img + b * C * HW + (long)(2 * y) * W + 2 * x;
+  const int dr = hasr ? W : 0, dc = hasc ? 1 : 0;          // the clamped second row / column
+  const float lvl = GRAD ? 0.f : sigma[b];
+  T* o = out + t * ldc;
+  for (int k = 0; k < ldc; k += 8) {
+    float v[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int c = k / 4 + h;
+      float q[4] = {0.f, 0.f, 0.f, 0.f};
+      if (c < C) {
+        const float* p = p0 + c * HW;
+        if (PAIR) {   // (W even: hasc holds for every x)
+          const float2 a = *(const float2*)p, d = *(const float2*)(p + dr);
+          q[0] = a.x, q[1] = a.y, q[2] = d.x, q[3] = d.y;
+        } else {
+          q[0] = p[0], q[1] = p[dc], q[2] = p[dr], q[3] = p[dr + dc];
+        }
+        if (GRAD) {
+          if (!hasc) q[1] = q[3] = 0.f;
+          if (!hasr) q[2] = q[3] = 0.f;
+        }
+      } else if (c == C) {
+        q[0] = lvl;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[4 * h + j] = q[j];
+    }
+    ffd_store8(o + k, v);
+  }
+}
+
 // I: index type (int when every index fits: 32-bit divisions are a fraction of the 64-bit ones)
 // CH: Charbonnier (models/loss.py:208-218) sqrt(d^2 + eps) with gradient d / sqrt(d^2 + eps), else L1
 template <typename T, typename I, bool CH>
@@ -1089,6 +1150,38 @@ extern "C" int kair_image_to_nhwc_hilo(const float* img, void* out, int ldc, con
   const long total = (long)B * H * W * ldc;
   KAIR_LAUNCH(image_to_nhwc_hilo_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, img, (bf16*)out,
                      ldc, mean, img_range, C, (long)H * W, total);
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kair_ffd_pack(const float* img, const float* sigma, void* out, int dtype, int ldc, int B, int C, int H, int W,
+                             void* stream) {
+  KAIR_CHECK_ARG(img && out, "ffd_pack: null pointer");
+  KAIR_CHECK_ARG(dtype == KAIR_F32 || dtype == KAIR_BF16, "ffd_pack: out dtype %d (fp32 or bf16)", dtype);
+  KAIR_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "ffd_pack: bad sizes (B %d, C %d, %dx%d)", B, C, H, W);
+  KAIR_CHECK_ARG(ldc % 8 == 0 && ldc >= 4 * C + (sigma ? 1 : 0),
+                 "ffd_pack: ldc %d must be a multiple of 8 holding %d channels", ldc, 4 * C + (sigma ? 1 : 0));
+  KAIR_CHECK_ARG(((uintptr_t)out & 15) == 0, "ffd_pack: out must be 16-byte aligned");
+  const int Hh = (H + 1) / 2, Wh = (W + 1) / 2;
+  const long npix = (long)B * Hh * Wh;
+  KAIR_CHECK_ARG((npix + 255) / 256 < (1L << 31), "ffd_pack: too many pixels");
+  const bool pair = W % 2 == 0 && ((uintptr_t)img & 7) == 0;
+  hipStream_t s = (hipStream_t)stream;
+#define KAIR_FFD_PACK(T, G, P)                                                                                         \
+  KAIR_LAUNCH((ffd_pack_kernel<T, G, P>), dim3((unsigned)nblk(npix, 256)), dim3(256), 0, s, img, sigma, (T*)out, ldc, C, \
+              H, W, Hh, Wh, npix)
+  if (dtype == KAIR_BF16) {
+    if (!sigma && pair) KAIR_FFD_PACK(bf16, true, true);
+    else if (!sigma) KAIR_FFD_PACK(bf16, true, false);
+    else if (pair) KAIR_FFD_PACK(bf16, false, true);
+    else KAIR_FFD_PACK(bf16, false, false);
+  } else {
+    if (!sigma && pair) KAIR_FFD_PACK(float, true, true);
+    else if (!sigma) KAIR_FFD_PACK(float, true, false);
+    else if (pair) KAIR_FFD_PACK(float, false, true);
+    else KAIR_FFD_PACK(float, false, false);
+  }
+#undef KAIR_FFD_PACK
   KAIR_CHECK_LAUNCH();
   return 0;
 }

@@ -155,24 +155,30 @@ __global__ __launch_bounds__(256) void synth_dn_kernel(const float* __restrict__
 // consecutive lanes (outH within each channel plane) and the augment's gather stays on the pool read.  The normals'
 // counter is the element index of the [B][C][PS][PS] noisy block -- synth_dn_kernel's, whose L an all-equal table
 // reproduces bit for bit.  image / rnd_h / rnd_w are clamped into the pool.
+template <bool MAP>
 __global__ __launch_bounds__(256) void synth_dn_map_kernel(const float* __restrict__ pool, int N, int C, int Hs, int Ws,
                                                            const int* __restrict__ par, int pstride, int scol, int B,
                                                            int PS, unsigned long long seed, unsigned long long step,
-                                                           float* __restrict__ outH, float* __restrict__ outL) {
-  const long n = (long)B * (C + 1) * PS * PS;
+                                                           float* __restrict__ outH, float* __restrict__ outL,
+                                                           float* __restrict__ outC) {
+  // MAP: outL [B][C + 1][PS][PS] with the level map as its last channel (DatasetFDnCNN); otherwise outL
+  // [B][C][PS][PS] and the level itself in outC[b] (DatasetFFDNet) -- the same H, normals and levels either way
+  const int CL = MAP ? C + 1 : C;
+  const long n = (long)B * CL * PS * PS;
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const int j = (int)(t % PS);
   long r = t / PS;
   const int i = (int)(r % PS);
   r /= PS;
-  const int c = (int)(r % (C + 1)), b = (int)(r / (C + 1));
+  const int c = (int)(r % CL), b = (int)(r / CL);
   const int* pr = par + (long)b * pstride;   // {image, rnd_h, rnd_w, mode}, ..., [scol] = float bits of sigma_b
   const float sigma = __int_as_float(pr[scol]);
-  if (c == C) {
+  if (MAP && c == C) {
     outL[t] = sigma;
     return;
   }
+  if (!MAP && c == 0 && i == 0 && j == 0) outC[b] = sigma;
   const int img = min(max(pr[0], 0), N - 1), rh = min(max(pr[1], 0), Hs - PS), rw = min(max(pr[2], 0), Ws - PS);
   int si, sj;
   aug_src(pr[3] & 7, i, j, PS, si, sj);
@@ -225,17 +231,35 @@ extern "C" int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int
   return 0;
 }
 
+static int synth_dn_levels(const char* who, bool map, const float* pool, int N, int C, int Hs, int Ws, const int* params,
+                           int pstride, int scol, int B, int PS, unsigned long long seed, unsigned long long step,
+                           float* outH, float* outL, float* outC, void* stream) {
+  KAIR_CHECK_ARG(pool && params && outH && outL && (map || outC), "%s: null pointer", who);
+  KAIR_CHECK_ARG(N > 0 && C > 0 && B > 0 && PS > 0 && PS <= Hs && PS <= Ws, "%s: bad sizes", who);
+  KAIR_CHECK_ARG(pstride >= 5 && scol >= 4 && scol < pstride, "%s: level column %d outside rows of %d ints", who, scol,
+                 pstride);
+  const long total = (long)B * (map ? C + 1 : C) * PS * PS;
+  KAIR_CHECK_ARG(nblocks(total) < (1L << 31), "%s: too many elements", who);
+  if (map)
+    KAIR_LAUNCH(synth_dn_map_kernel<true>, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, N, C,
+                Hs, Ws, params, pstride, scol, B, PS, seed, step, outH, outL, outC);
+  else
+    KAIR_LAUNCH(synth_dn_map_kernel<false>, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, N, C,
+                Hs, Ws, params, pstride, scol, B, PS, seed, step, outH, outL, outC);
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int kair_synth_dn_map(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol,
                                  int B, int PS, unsigned long long seed, unsigned long long step, float* outH,
                                  float* outL, void* stream) {
-  KAIR_CHECK_ARG(pool && params && outH && outL, "synth_dn_map: null pointer");
-  KAIR_CHECK_ARG(N > 0 && C > 0 && B > 0 && PS > 0 && PS <= Hs && PS <= Ws, "synth_dn_map: bad sizes");
-  KAIR_CHECK_ARG(pstride >= 5 && scol >= 4 && scol < pstride, "synth_dn_map: level column %d outside rows of %d ints",
-                 scol, pstride);
-  const long total = (long)B * (C + 1) * PS * PS;
-  KAIR_CHECK_ARG(nblocks(total) < (1L << 31), "synth_dn_map: too many elements");
-  KAIR_LAUNCH(synth_dn_map_kernel, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, N, C, Hs, Ws,
-                     params, pstride, scol, B, PS, seed, step, outH, outL);
-  KAIR_CHECK_LAUNCH();
-  return 0;
+  return synth_dn_levels("synth_dn_map", true, pool, N, C, Hs, Ws, params, pstride, scol, B, PS, seed, step, outH, outL,
+                         nullptr, stream);
+}
+
+extern "C" int kair_synth_dn_level(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride,
+                                   int scol, int B, int PS, unsigned long long seed, unsigned long long step, float* outH,
+                                   float* outL, float* outC, void* stream) {
+  return synth_dn_levels("synth_dn_level", false, pool, N, C, Hs, Ws, params, pstride, scol, B, PS, seed, step, outH, outL,
+                         outC, stream);
 }

@@ -69,6 +69,16 @@ Per sample, in this order: the image, rnd_h, rnd_w, the augment mode, then sigma
 (kair_synth_dn_map, csrc/synth.hip) does the crop, the augment, the per-sample AWGN (kair_synth_dn's Philox normals) and
 the map channel.  `last_params` is the [B, 5] int32 table {image, rnd_h, rnd_w, mode} plus the float32 bits of
 sigma / 255 (`last_params[:, 4:].view(torch.float32)`).
+
+task="ffdnet" makes DatasetFFDNet batches (data/dataset_ffdnet.py) for FFDNet: the same draws (_draw_fdncnn), Philox key
+and counters, but the level is a second tensor instead of a map channel.
+
+    synth = PatchSynth(pool, task="ffdnet", H_size=64, sigma=(0, 75), seed=0)
+    L, H, C = synth.next(64)                     # [B, C, 64, 64] twice, the levels sigma / 255 as [B, 1, 1, 1]
+    model.feed_data(synth.next_dict(64))         # the {"L", "H", "C"} dict ModelPlain2.feed_data reads
+
+One launch (kair_synth_dn_level: kair_synth_dn_map's device code); with the same arguments L equals task "fdncnn"'s
+L[:, :C] and C its map value, bit for bit.
 """
 import math
 import random
@@ -123,10 +133,10 @@ class PatchSynth:
                                  "keep the colour JPEG's minimum width of 5)")
             self.lq, self.bsr_sf, self.debug_stages = int(lq_patchsize), int(scale), bool(debug_stages)
             self._noise_off = False   # tests only: utils_blindsr.draw_bsrgan(noise_off=True)
-        if task == "fdncnn":
+        if task in ("fdncnn", "ffdnet"):
             self.sigma_range = tuple(float(v) for v in sigma) if isinstance(sigma, (tuple, list)) else (float(sigma),) * 2
             if len(self.sigma_range) != 2 or not 0 <= self.sigma_range[0] <= self.sigma_range[1]:
-                raise ValueError(f"PatchSynth: task 'fdncnn' takes sigma as (min, max), 0 <= min <= max (got {sigma!r})")
+                raise ValueError(f"PatchSynth: task '{task}' takes sigma as (min, max), 0 <= min <= max (got {sigma!r})")
             sigma = self.sigma_range[1]
         self.sf = scale if task == "sr" else 1
         Hs, Ws = pool.shape[-2:]
@@ -153,7 +163,7 @@ class PatchSynth:
             ih, wh = util.bicubic_taps(self.PS, self.PS // 2, 0.5)   # the MATLAB x1/2 of slot 0
             self.taps_half = (ih.to(dev), wh.to(dev), ih.to(dev), wh.to(dev), self.PS, self.PS)
             self._bsr_ws = None
-        elif task not in ("dn", "usrnet", "jpeg", "fdncnn"):
+        elif task not in ("dn", "usrnet", "jpeg", "fdncnn", "ffdnet"):
             raise ValueError(task)
         self._par_host = None
         self._par_ev = None
@@ -185,14 +195,15 @@ class PatchSynth:
     def next(self, B, out=None):
         """The next batch (L, H), produced on the current stream.  The per-sample geometry goes up
         through a pinned staging buffer with an async copy, so a training loop that calls next()
-        every step never blocks the host on the device.  task "usrnet": (L, H, k, sf, sigma)."""
+        every step never blocks the host on the device.  task "usrnet": (L, H, k, sf, sigma); task "ffdnet":
+        (L, H, C), C the levels [B, 1, 1, 1]."""
         if self.task == "usrnet":
             return self._next_usr(B)
         if self.task == "blindsr":
             return self._next_blindsr(B)
         dev = self.pool.device
-        jpeg, fdn = self.task == "jpeg", self.task == "fdncnn"
-        host = self._draw_jpeg(B) if jpeg else self._draw_fdncnn(B) if fdn else self.draw(B)
+        jpeg, fdn, ffd = self.task == "jpeg", self.task == "fdncnn", self.task == "ffdnet"
+        host = self._draw_jpeg(B) if jpeg else self._draw_fdncnn(B) if fdn or ffd else self.draw(B)
         if self._par_host is None or self._par_host.shape[0] < B:
             self._par_host = torch.empty(B, host.shape[1], dtype=torch.int32).pin_memory()
             self._par_ev = None
@@ -213,16 +224,19 @@ class PatchSynth:
             H.synth_jpeg(self.pool, par, B, self.PS, self.is_color, Hp, Lp)
         elif fdn:
             H.synth_dn_map(self.pool, par, B, self.PS, self.seed, self.step, Hp, Lp)
+        elif ffd:
+            Cp = torch.empty(B, 1, 1, 1, device=dev)
+            H.synth_dn_level(self.pool, par, B, self.PS, self.seed, self.step, Hp, Lp, Cp)
         elif self.task == "sr":
             H.synth_sr(self.pool, par, B, self.PS, self.sf, self.taps_h, self.taps_w, Hp, Lp)
         else:
             H.synth_dn(self.pool, par, B, self.PS, self.sigma, self.seed, self.step, Hp, Lp)
         self.step += 1
         self.last_params = par
-        return Lp, Hp
+        return (Lp, Hp, Cp) if ffd else (Lp, Hp)
 
     def _draw_fdncnn(self, B):
-        """Host draws of the next FDnCNN / DRUNet batch: [B, 5] int32 {image, rnd_h, rnd_w, mode, bits of sigma / 255}."""
+        """Host draws of the next FDnCNN / DRUNet / FFDNet batch: [B, 5] int32 {image, rnd_h, rnd_w, mode, bits of sigma / 255}."""
         ints = torch.zeros(B, 5, dtype=torch.int32)
         lev = torch.zeros(B, 1, dtype=torch.float32)
         for b in range(B):
@@ -360,12 +374,15 @@ class PatchSynth:
 
     def next_dict(self, B):
         """The next USRNet batch as the dict ModelPlain4.feed_data reads (sf an int64 tensor [B]); task "fdncnn": the
-        {"L", "H"} dict ModelPlain.feed_data reads."""
+        {"L", "H"} dict ModelPlain.feed_data reads; task "ffdnet": {"L", "H", "C"} for ModelPlain2.feed_data."""
+        if self.task == "ffdnet":
+            L, Hh, C = self.next(B)
+            return {"L": L, "H": Hh, "C": C}
         if self.task == "fdncnn":
             L, Hh = self.next(B)
             return {"L": L, "H": Hh}
         if self.task != "usrnet":
-            raise ValueError("PatchSynth.next_dict: tasks 'usrnet' and 'fdncnn' only")
+            raise ValueError("PatchSynth.next_dict: tasks 'usrnet', 'fdncnn' and 'ffdnet' only")
         L, Hh, k, sf, sigma = self._next_usr(B)
         return {"L": L, "H": Hh, "k": k, "sf": torch.full((B,), sf, dtype=torch.int64), "sigma": sigma}
 

@@ -1,6 +1,7 @@
 """Dataset factory (mirror of /root/reference/data/select_dataset.py:12-100) for the datasets that
 feed the kair_amd hot path: 'dncnn' (DatasetDnCNN, config 1), 'fdncnn' / 'drunet' (DatasetFDnCNN: the noisy image
-plus its noise-level map, train_fdncnn.json and train_drunet.json), 'sr' (DatasetSR, configs 2/4/5),
+plus its noise-level map, train_fdncnn.json and train_drunet.json), 'ffdnet' (DatasetFFDNet: the noisy image and its
+noise level as a second input "C"), 'sr' (DatasetSR, configs 2/4/5),
 'usrnet' (DatasetUSRNet, config 3), 'jpeg' (DatasetJPEG, the JPEG artifact-reduction SwinIR of
 train_swinir_car_jpeg.json) and 'blindsr' (DatasetBlindSR, the BSRGAN degradation of
 train_bsrgan_x4_psnr.json and train_swinir_sr_realworld_x4_psnr.json).
@@ -13,6 +14,8 @@ def define_Dataset(dataset_opt):
         from .dataset_dncnn import DatasetDnCNN as D
     elif t in ("fdncnn", "drunet"):
         from .dataset_fdncnn import DatasetFDnCNN as D
+    elif t == "ffdnet":
+        from .dataset_ffdnet import DatasetFFDNet as D
     elif t in ("sr", "super-resolution"):
         from .dataset_sr import DatasetSR as D
     elif t == "usrnet":
@@ -22,5 +25,5 @@ def define_Dataset(dataset_opt):
     elif t in ("blindsr", "bsrnet", "bsrgan"):
         from .dataset_blindsr import DatasetBlindSR as D
     else:
-        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, fdncnn, drunet, sr, usrnet, jpeg, blindsr).")
+        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, fdncnn, drunet, ffdnet, sr, usrnet, jpeg, blindsr).")
     return D(dataset_opt)

@@ -300,14 +300,16 @@ class ConvNetFunction(torch.autograd.Function):
     node leases its plan from forward to backward (kair_amd/engine/plans.py)."""
 
     @classmethod
-    def run(cls, engine, x, params):
-        return cls.apply(engine, autograd_mode(params), x, *params)
+    def run(cls, engine, x, params, *cond):
+        """cond: extra, non-differentiable forward inputs handed to engine.forward after x (FFDNet: sigma)."""
+        return cls.apply(engine, autograd_mode(params), len(cond), x, *cond, *params)
 
     @staticmethod
-    def forward(ctx, engine, mode, x, *params):
+    def forward(ctx, engine, mode, n_cond, x, *rest):
+        cond, params = rest[:n_cond], rest[n_cond:]
         with plan_mode(engine, mode):
-            E = engine.forward(x.float().contiguous())
-        ctx.engine, ctx.params = engine, params
+            E = engine.forward(x.float().contiguous(), *cond)
+        ctx.engine, ctx.params, ctx.n_cond = engine, params, n_cond
         ctx.lease = Lease(engine.cur) if mode == "lease" else None
         return E.clone()
 
@@ -316,4 +318,4 @@ class ConvNetFunction(torch.autograd.Function):
         _, grads = lease_grads(ctx, gE)
         ctx.engine.backward_from_grad(gE.float(), grads)
         ctx.lease.release()
-        return (None, None, None) + tuple(grads[p] for p in ctx.params)
+        return (None,) * (4 + ctx.n_cond) + tuple(grads[p] for p in ctx.params)

@@ -1,4 +1,4 @@
-"""DnCNN / FDnCNN step program for MI355X.
+"""DnCNN / FDnCNN / FFDNet step program for MI355X.
 
 Reference: /root/reference/models/network_dncnn.py:40-71 (DnCNN, out = x - model(x)), 128-149
 (FDnCNN, out = model(x)); layers from basicblock.conv (basicblock.py:61-98).  SURVEY §8 row a14.
@@ -9,6 +9,9 @@ the activation fused into the normalise pass -> compute-dtype activation rows fo
 Without BN the activation is fused into the conv epilogue.  Backward: BN backward fuses the
 activation gate and the two per-channel reductions; conv input / weight / bias gradients as in the
 other conv programs.
+
+FFDNetEngine (below) runs the same layer loop over the half grid behind a PixelUnshuffle head (kair_ffd_pack) and a
+PixelShuffle store; DnCNNEngine keeps what differs in the six methods after convs().
 """
 import torch
 import torch.nn as nn
@@ -55,8 +58,31 @@ class DnCNNEngine(ConvEngineBase):
     def convs(self):
         return [c for c, _, _, _ in self.layers]
 
-    def _build_plan(self, key, infer):
+    # ---- what a network with another head / tail overrides (FFDNetEngine) ----------------------
+    def _grid(self, key):
+        """The conv grid (rows, columns) of the plan keyed (B, h, w): the image itself."""
+        return key[1], key[2]
+
+    def _out_image(self, P, key):
         B, Hh, Ww = key
+        return self._e(B, self.out_ch, Hh, Ww)
+
+    def _pack_input(self, P, x, *cond):
+        H.image_to_nhwc(x, P["xin"], self.Cin_p, None, 1.0, P["B"], self.in_ch, P["H"], P["W"])
+
+    def _out_epilogue(self, P, c):
+        return H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(None, 1.0, self.out_ch, P["H"], P["W"]))
+
+    def _loss(self, P, H_img, loss_weight, charb_eps):
+        H.l1_loss(P["E"], H_img, P["loss"], P["dEf"], 16, loss_weight, P["B"], self.out_ch, P["H"], P["W"], P["loss_ws"],
+                  charb_eps=charb_eps)
+
+    def _pack_grad(self, P, gE):
+        H.image_to_nhwc(gE.contiguous(), P["dEf"], 16, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])
+
+    def _build_plan(self, key, infer):
+        B = key[0]
+        Hh, Ww = self._grid(key)
         T, e, nc = self.tdt, self._e, self.nc
         M = B * Hh * Ww
         P = {"B": B, "H": Hh, "W": Ww, "M": M}
@@ -66,7 +92,7 @@ class DnCNNEngine(ConvEngineBase):
         P["z"] = [e(M, nc) if bn is not None else None for _, bn, _, _ in self.layers[:n_mid]]
         P["mean"] = [e(nc) if bn is not None else None for _, bn, _, _ in self.layers[:n_mid]]
         P["rstd"] = [e(nc) if bn is not None else None for _, bn, _, _ in self.layers[:n_mid]]
-        P["E"] = e(B, self.out_ch, Hh, Ww)
+        P["E"] = self._out_image(P, key)
         P["dEf"] = torch.zeros(M, 16, device=self.device)
         P["dn"] = e(M, 16, dt=T)
         P["G"], P["dz"] = e(M, nc), e(M, nc, dt=T)
@@ -78,17 +104,18 @@ class DnCNNEngine(ConvEngineBase):
         P["wg_ws"] = e(self.wgrad_ws_size(shapes))
         return P
 
-    def forward(self, x, drop_scales=None):
-        B, _, Hh, Ww = x.shape
-        P = self.plan(B, Hh, Ww)
+    def forward(self, x, *cond):
+        """cond: the network's extra forward inputs (FFDNet: sigma); the trainer's drop-path slot (None) otherwise."""
+        B, _, h, w = x.shape
+        P = self.plan(B, h, w)
         self.pack()
         cd, nc = self.cd, self.nc
-        M = P["M"]
+        M, Hh, Ww = P["M"], P["H"], P["W"]
         x = x.contiguous()
         self.cur = P
         P["x"] = x
         training = self.net_ref().training
-        H.image_to_nhwc(x, P["xin"], self.Cin_p, None, 1.0, B, self.in_ch, Hh, Ww)
+        self._pack_input(P, x, *cond)
         src, ldsrc, Cs = P["xin"], self.Cin_p, self.Cin_p
         for li, (c, bn, act, slope) in enumerate(self.layers[:-1]):
             a = P["a"][li]
@@ -105,22 +132,20 @@ class DnCNNEngine(ConvEngineBase):
                     bn.num_batches_tracked.add_(1)
             src, ldsrc, Cs = a, nc, nc
         c = self.layers[-1][0]
-        H.gemm_nt(H.im2col(src, Hh, Ww, nc), c.fwd(),
-                  H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(None, 1.0, self.out_ch, Hh, Ww)), M, c.Cop,
-                  9 * nc, cd)
+        H.gemm_nt(H.im2col(src, Hh, Ww, nc), c.fwd(), self._out_epilogue(P, c), M, c.Cop, 9 * nc, cd)
         if self.residual:
             H.axpby(P["E"], x, 1.0, -1.0)     # x - model(x)
         return P["E"]
 
     def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
         P = self.cur
-        H.l1_loss(P["E"], H_img, P["loss"], P["dEf"], 16, loss_weight, P["B"], self.out_ch, P["H"], P["W"], P["loss_ws"], charb_eps=charb_eps)
+        self._loss(P, H_img, loss_weight, charb_eps)
         self.backward(grads, P)
         return P["loss"]
 
     def backward_from_grad(self, gE, grads):
         P = self.cur
-        H.image_to_nhwc(gE.contiguous(), P["dEf"], 16, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])
+        self._pack_grad(P, gE)
         self.backward(grads, P)
 
     def backward(self, grads, P):
@@ -149,3 +174,57 @@ class DnCNNEngine(ConvEngineBase):
                 self.conv_wgrad(P, c, dz, nc, H.im2col(P["a"][li - 1], Hh, Ww, nc), M, grads, *bs)
             else:
                 self.conv_wgrad(P, c, dz, nc, H.im2col(P["xin"], Hh, Ww, self.Cin_p), M, grads, *bs)
+
+
+class FFDNetEngine(DnCNNEngine):
+    """FFDNet (the restated reference forward, network_ffdnet.FFDNet): DnCNN's layer loop over the half grid.
+
+    head: kair_ffd_pack -- ReplicationPad2d to even sizes, PixelUnshuffle(2) and the per-sample noise level as channel
+          4 in_nc of the packed rows, one launch;
+    tail: the last conv stores through KAIR_OUT_PSHUF_NCHW (ps_r = 2) straight into the NCHW image; an odd h or w
+          stores into a plan-owned padded image whose [..., :h, :w] view is the output.
+    Plans are keyed (B, h, w); the conv grid is ceil(h/2) x ceil(w/2).  out = model(x): no residual."""
+
+    def __init__(self, net, compute_dtype="bf16"):
+        super().__init__(net, compute_dtype, residual=False)
+        if (self.in_ch - 1) % 4 or self.out_ch % 4:
+            raise NotImplementedError("kair_amd FFDNet: the first conv reads 4 in_nc + 1 channels, the last writes 4 out_nc")
+        self.img_in, self.img_out = (self.in_ch - 1) // 4, self.out_ch // 4
+
+    def _grid(self, key):
+        return (key[1] + 1) // 2, (key[2] + 1) // 2
+
+    def _out_image(self, P, key):
+        B, h, w = key
+        P["h"], P["w"] = h, w
+        P["Epad"] = self._e(B, self.img_out, 2 * P["H"], 2 * P["W"])
+        return P["Epad"][..., :h, :w]   # (the whole image when h and w are even)
+
+    def sigma_rows(self, sigma, B):
+        """[B, 1, 1, 1], [B] or one element (broadcast) -> [B] fp32 on the device."""
+        s = torch.as_tensor(sigma, dtype=torch.float32, device=self.device).reshape(-1)
+        if s.numel() == 1 and B > 1:
+            s = s.expand(B)
+        if s.numel() != B:
+            raise ValueError(f"kair_amd FFDNet: sigma holds {s.numel()} levels for a batch of {B}")
+        return s.contiguous()
+
+    def _pack_input(self, P, x, sigma=None):
+        if sigma is None:
+            raise ValueError("kair_amd FFDNet: forward(x, sigma) needs the noise level")
+        P["sigma"] = self.sigma_rows(sigma, P["B"])
+        H.ffd_pack(x, P["sigma"], P["xin"], self.Cin_p, P["B"], self.img_in, P["h"], P["w"])
+
+    def _out_epilogue(self, P, c):
+        return H.epilogue(P["Epad"], mode=H.OUT_PSHUF_NCHW, ldo=0, bias=c.bp, ps=(2, P["H"], P["W"]),
+                          img=(None, 1.0, self.img_out, P["H"], P["W"]))
+
+    def _loss(self, P, H_img, loss_weight, charb_eps):
+        if P["h"] % 2 or P["w"] % 2:
+            raise ValueError(f"kair_amd FFDNet: the fused loss needs even sizes (got {P['h']} x {P['w']}); odd sizes run "
+                             "forward and the autograd backward")
+        H.l1_loss(P["Epad"], H_img, P["loss"], P["dEf"], 16, loss_weight, P["B"], self.img_out, P["h"], P["w"],
+                  P["loss_ws"], ps_r=2, charb_eps=charb_eps)
+
+    def _pack_grad(self, P, gE):
+        H.ffd_pack(gE.contiguous(), None, P["dEf"], 16, P["B"], self.img_out, P["h"], P["w"])
