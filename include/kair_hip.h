@@ -555,6 +555,20 @@ int kair_l1_loss(const float* E, const float* H, float* loss_out, void* dE, int 
  * kair_l1_loss. */
 int kair_charbonnier_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r,
                           float weight, float eps, int B, int C, int Hh, int Ww, float* ws, void* stream);
+/* SSIM as a loss (G_lossfn_type 'ssim'; the reference's models/loss_ssim.py restated in kair_amd/models/model_plain.py
+ * SSIMLoss): 11x11 Gaussian window (sigma 1.5, sum 1), depthwise, zero padding 5, C1 = 0.01^2, C2 = 0.03^2 (data
+ * range 1), loss_out[0] = weight * mean over B, C, H, W of the SSIM map -- the SSIM itself, not 1 - SSIM: a run that
+ * maximises it passes a negative weight.  dE = d loss_out / dE (analytic), in kair_l1_loss's rows layout (dtype
+ * KAIR_F32 / KAIR_BF16, ldc slots per pixel of the [Hh/ps_r, Ww/ps_r] grid, slot = c*r*r + (y%r)*r + x%r, slots
+ * >= C*r*r zero), or as the fp32 NCHW image gradient [B][C][Hh][Ww] (kair_ssim_loss_nchw).  E, H: NCHW fp32.
+ * workspace: kair_ssim_workspace_bytes(B, C, Hh, Ww) bytes, 16-byte aligned (three fp32 planes the size of E + one
+ * partial sum per 32x32 tile; summed in a fixed order: repeated calls are bit-identical).  Argument errors (null
+ * pointer, Hh or Ww not divisible by ps_r, C*ps_r^2 > ldc, misaligned workspace) launch nothing. */
+long kair_ssim_workspace_bytes(int B, int C, int H, int W);
+int kair_ssim_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r, float weight,
+                   int B, int C, int Hh, int Ww, void* workspace, void* stream);
+int kair_ssim_loss_nchw(const float* E, const float* H, float* loss_out, float* dE, float weight, int B, int C, int Hh,
+                        int Ww, void* workspace, void* stream);
 /* y[i] += a * x[i] over n fp32 elements (residual-gradient merges). */
 int kair_axpy(float* y, const float* x, float a, long n, void* stream);
 /* BatchNorm2d over NHWC rows z [M, C] fp32 (basicblock.py:69: momentum 0.9, eps 1e-4), fused act

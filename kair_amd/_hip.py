@@ -177,6 +177,9 @@ _SIGS = {
     "kair_conv3x3_narrow_wgrad_x3": [c_vp, c_long, c_int, c_vp, c_long, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
                                      c_int, c_int, c_vp],
     "kair_l1_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_ssim_workspace_bytes": [c_int, c_int, c_int, c_int],
+    "kair_ssim_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_ssim_loss_nchw": [c_vp, c_vp, c_vp, c_vp, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp],
     "kair_charbonnier_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int,
                               c_vp, c_vp],
     "kair_axpy": [c_vp, c_vp, c_float, c_long, c_vp],
@@ -262,7 +265,7 @@ _SIGS = {
 _RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_colsum_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
-            "kair_jpeg_workspace_bytes": c_long}
+            "kair_jpeg_workspace_bytes": c_long, "kair_ssim_workspace_bytes": c_long}
 
 _lib = None
 
@@ -813,6 +816,31 @@ def l1_loss(E, H, loss_out, dE, ldc, weight, B, C, Hh, Ww, ws, ps_r=1, charb_eps
         return
     check(lib().kair_l1_loss(ptr(E), ptr(H), ptr(loss_out), ptr(dE), dtype_code(dE), ldc, ps_r, weight, B, C, Hh, Ww,
                              ptr(ws), stream_ptr()), "l1_loss")
+
+
+def ssim_workspace_bytes(B, C, Hh, Ww):
+    """kair_ssim_workspace_bytes: the workspace of one ssim_loss call on [B, C, Hh, Ww] images."""
+    return lib().kair_ssim_workspace_bytes(B, C, Hh, Ww)
+
+
+def ssim_workspace(B, C, Hh, Ww, device):
+    return torch.empty(ssim_workspace_bytes(B, C, Hh, Ww), dtype=torch.uint8, device=device)
+
+
+def ssim_loss(E, H, loss_out, dE, ldc, weight, B, C, Hh, Ww, ws, ps_r=1):
+    """weight * mean SSIM(E, H) (the SSIM itself: maximising it takes a negative weight) + its gradient, in
+    l1_loss's rows layout; ldc None: dE is the fp32 NCHW image gradient.  ws: ssim_workspace(B, C, Hh, Ww)."""
+    if ws.numel() * ws.element_size() < ssim_workspace_bytes(B, C, Hh, Ww):
+        raise ValueError(f"kair_ssim_loss: workspace too small ({ws.numel() * ws.element_size()} < "
+                         f"{ssim_workspace_bytes(B, C, Hh, Ww)} bytes)")
+    if ldc is None:
+        if dE.dtype != torch.float32:
+            raise TypeError("kair_ssim_loss_nchw: the image gradient is fp32")
+        check(lib().kair_ssim_loss_nchw(ptr(E), ptr(H), ptr(loss_out), ptr(dE), weight, B, C, Hh, Ww, ptr(ws),
+                                        stream_ptr()), "ssim_loss_nchw")
+        return
+    check(lib().kair_ssim_loss(ptr(E), ptr(H), ptr(loss_out), ptr(dE), dtype_code(dE), ldc, ps_r, weight, B, C, Hh, Ww,
+                               ptr(ws), stream_ptr()), "ssim_loss")
 
 
 def axpy(y, x, a, n=None):

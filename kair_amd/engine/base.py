@@ -3,7 +3,7 @@ engine, and the plumbing every engine shares.
 
 An engine is the launch sequence of one network over preallocated HBM buffers ("plans", plans.py).  Its drivers use
   forward(x, ...) -> the output buffer; sets `cur`, the plan the backward reads
-  backward_from_loss(H, grads, loss_weight, charb_eps) -> the device loss [1]    (FusedTrainer)
+  backward_from_loss(H, grads, loss_weight, charb_eps, loss_type) -> the device loss [1]    (FusedTrainer)
   backward_from_grad(gE, grads)                                                  (the autograd Functions)
   cur, plan_mode, _packed_version (reset by whoever changes the weights), repack_always
   blocks (objects with a drop-path rate .dp; empty without stochastic depth), drop_path_scales()
@@ -191,11 +191,36 @@ class EngineBase:
             self.seg_hook()
 
     # ---- fp32x3 exponents and the range guard's reaction --------------------------------------
-    def _x3_grad_exp(self, numel, weight=1.0):
+    def _x3_grad_exp(self, numel, weight=1.0, loss_type=None):
         """The fp32x3 gradient exponent: the mean-loss gradient is O(weight / numel) per output element (weight: the
         loss weight over img_range), so data gradients times 2^(log2(numel / weight) + 4) sit near 2^4 at the loss,
-        2^12 below fp16's overflow."""
-        return int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
+        2^12 below fp16's overflow.  'ssim': numel |dS/dE| is not bounded by 1 -- X3_SSIM_HEADROOM binades lower."""
+        e = int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
+        return e - self.X3_SSIM_HEADROOM if loss_type == "ssim" else e
+
+    # numel |dS/dE| of the SSIM loss: <= ~4 / C2 + 1 / sqrt(C1) ~ 2^12 for images in [0, 1] (flat patches that differ
+    # by a constant; 2^6.3 measured on such a pair), <= 2^5.1 measured in float64 over the SSIM tests' inputs and
+    # crops of the golden test images (DESIGN.md section 7, "SSIM loss").  6 binades put the measured worst case at
+    # 2^(4 + 5.1 - 6) ~ 2^3 at the loss, beside L1's 2^4, and the analytic worst case at 2^10 < fp16's 2^16; typical
+    # gradients (numel |dS/dE| ~ 1) drop to 2^-2, their lo halves (2^-13) still normal fp16 numbers (>= 2^-14).
+    # The range guard stays the backstop.
+    X3_SSIM_HEADROOM = 6
+
+    def pixel_loss(self, P, E, H_img, dE, ldc, weight, C, Hh, Ww, ps_r=1, charb_eps=None, loss_type=None):
+        """The one dispatch of every engine's loss hook: loss_type None / 'l1' / 'charbonnier' (charb_eps set) ->
+        kair_l1_loss / kair_charbonnier_loss; 'ssim' -> kair_ssim_loss, whose workspace joins the plan on the first
+        SSIM step (an eager warm-up step: before any capture), so L1 plans stay as they were.  Loss into P['loss'],
+        gradient rows into dE."""
+        if loss_type == "ssim":
+            ws = P.get("ssim_ws")
+            if ws is None:
+                ws = P["ssim_ws"] = H.ssim_workspace(P["B"], C, Hh, Ww, self.device)
+            H.ssim_loss(E, H_img, P["loss"], dE, ldc, weight, P["B"], C, Hh, Ww, ws, ps_r=ps_r)
+        elif loss_type in (None, "l1", "charbonnier"):
+            H.l1_loss(E, H_img, P["loss"], dE, ldc, weight, P["B"], C, Hh, Ww, P["loss_ws"], ps_r=ps_r,
+                      charb_eps=charb_eps)
+        else:
+            raise NotImplementedError(f"fused pixel loss {loss_type!r}")
 
     @staticmethod
     def x3_upstream_grad_exp(mx):

@@ -73,9 +73,9 @@ class DnCNNEngine(ConvEngineBase):
     def _out_epilogue(self, P, c):
         return H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(None, 1.0, self.out_ch, P["H"], P["W"]))
 
-    def _loss(self, P, H_img, loss_weight, charb_eps):
-        H.l1_loss(P["E"], H_img, P["loss"], P["dEf"], 16, loss_weight, P["B"], self.out_ch, P["H"], P["W"], P["loss_ws"],
-                  charb_eps=charb_eps)
+    def _loss(self, P, H_img, loss_weight, charb_eps, loss_type=None):
+        self.pixel_loss(P, P["E"], H_img, P["dEf"], 16, loss_weight, self.out_ch, P["H"], P["W"], charb_eps=charb_eps,
+                        loss_type=loss_type)
 
     def _pack_grad(self, P, gE):
         H.image_to_nhwc(gE.contiguous(), P["dEf"], 16, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])
@@ -137,9 +137,9 @@ class DnCNNEngine(ConvEngineBase):
             H.axpby(P["E"], x, 1.0, -1.0)     # x - model(x)
         return P["E"]
 
-    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
+    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None, loss_type=None):
         P = self.cur
-        self._loss(P, H_img, loss_weight, charb_eps)
+        self._loss(P, H_img, loss_weight, charb_eps, loss_type)
         self.backward(grads, P)
         return P["loss"]
 
@@ -219,12 +219,12 @@ class FFDNetEngine(DnCNNEngine):
         return H.epilogue(P["Epad"], mode=H.OUT_PSHUF_NCHW, ldo=0, bias=c.bp, ps=(2, P["H"], P["W"]),
                           img=(None, 1.0, self.img_out, P["H"], P["W"]))
 
-    def _loss(self, P, H_img, loss_weight, charb_eps):
+    def _loss(self, P, H_img, loss_weight, charb_eps, loss_type=None):
         if P["h"] % 2 or P["w"] % 2:
             raise ValueError(f"kair_amd FFDNet: the fused loss needs even sizes (got {P['h']} x {P['w']}); odd sizes run "
                              "forward and the autograd backward")
-        H.l1_loss(P["Epad"], H_img, P["loss"], P["dEf"], 16, loss_weight, P["B"], self.img_out, P["h"], P["w"],
-                  P["loss_ws"], ps_r=2, charb_eps=charb_eps)
+        self.pixel_loss(P, P["Epad"], H_img, P["dEf"], 16, loss_weight, self.img_out, P["h"], P["w"], ps_r=2,
+                        charb_eps=charb_eps, loss_type=loss_type)
 
     def _pack_grad(self, P, gE):
         H.ffd_pack(gE.contiguous(), None, P["dEf"], 16, P["B"], self.img_out, P["h"], P["w"])

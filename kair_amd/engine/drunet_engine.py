@@ -57,11 +57,11 @@ class DRUNetEngine(ResUNetProgram):
         self._unet_fwd(P, P["S"], P["xin"], P["E"])
         return P["E"]
 
-    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
+    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None, loss_type=None):
         P = self.cur
-        H.l1_loss(P["E"], H_img, P["loss"], P["gE"], C8, loss_weight, P["B"], self.out_nc, P["H"], P["W"], P["loss_ws"],
-                  charb_eps=charb_eps)
-        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_nc * P["H"] * P["W"], loss_weight)
+        self.pixel_loss(P, P["E"], H_img, P["gE"], C8, loss_weight, self.out_nc, P["H"], P["W"], charb_eps=charb_eps,
+                        loss_type=loss_type)
+        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_nc * P["H"] * P["W"], loss_weight, loss_type)
         self.backward(grads, P)
         return P["loss"]
 

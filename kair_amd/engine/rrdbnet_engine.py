@@ -172,11 +172,12 @@ class RRDBNetEngine(ConvEngineBase):
         return P["E"]
 
     # ------------------------------------------------------------------------------------
-    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
+    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None, loss_type=None):
         P = self.cur
         HL, WL = P["levels"][-1]
-        H.l1_loss(P["E"], H_img, P["loss"], P["dE"], 16, loss_weight, P["B"], self.out_ch, HL, WL, P["loss_ws"], charb_eps=charb_eps)
-        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_ch * HL * WL, loss_weight)
+        self.pixel_loss(P, P["E"], H_img, P["dE"], 16, loss_weight, self.out_ch, HL, WL, charb_eps=charb_eps,
+                        loss_type=loss_type)
+        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_ch * HL * WL, loss_weight, loss_type)
         self.backward(grads, P)
         return P["loss"]
 

@@ -727,16 +727,17 @@ class SwinIREngine(EngineBase):
     def _bias_colsum(self, P, G, M, Np, layer_map, bgrad):
         H.colsum(G, M, Np, layer_map, bgrad, P["colsum_ws"])
 
-    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
-        """L1 loss (mean) against H_img, then the full backward.  grads: {param: fp32 tensor to write}.
-        Returns the device loss tensor [1]."""
+    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None, loss_type=None):
+        """L1 (or Charbonnier / SSIM) loss (mean) against H_img, then the full backward.  grads: {param: fp32 tensor
+        to write}.  Returns the device loss tensor [1]."""
         P = self.cur
         B, Hh, Ww = P["B"], P["H"], P["W"]
         # E = v / img_range + ...: dL/dv = dL/dE / img_range, folded into the loss kernel's gradient scale
-        # (which also scales the reported loss, undone below)
+        # (which also scales the reported loss, undone below).  P["E"] is the image-unit output whatever img_range is
+        # (the last epilogue stores v / img_range + mean), so the SSIM's absolute C1 / C2 see the scale net(x) has
         wr = loss_weight / self.img_range
-        P["e_g"] = self._x3_grad_exp(B * self.in_ch * Hh * self.scale * Ww * self.scale, wr)
-        self.tail.loss(self, P, H_img, wr, charb_eps)
+        P["e_g"] = self._x3_grad_exp(B * self.in_ch * Hh * self.scale * Ww * self.scale, wr, loss_type)
+        self.tail.loss(self, P, H_img, wr, charb_eps, loss_type)
         if self.img_range != 1.0:
             P["loss"].mul_(self.img_range)
         self.backward(grads, P)

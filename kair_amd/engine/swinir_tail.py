@@ -29,10 +29,10 @@ class _Tail:
         """Np of every eng._bias_colsum the tail's backward can issue (sizes P['colsum_ws'])."""
         return []
 
-    def loss(self, eng, P, H_img, wr, charb_eps):
-        """L1 / Charbonnier loss into P['loss'], its gradient into the P['dE'] rows."""
-        H.l1_loss(P["E"], H_img, P["loss"], P["dE"], P.get("dE_ld", 16), wr, P["B"], eng.in_ch, P["H"] * eng.scale,
-                  P["W"] * eng.scale, P["loss_ws"], charb_eps=charb_eps)
+    def loss(self, eng, P, H_img, wr, charb_eps, loss_type=None):
+        """L1 / Charbonnier / SSIM loss into P['loss'], its gradient into the P['dE'] rows."""
+        eng.pixel_loss(P, P["E"], H_img, P["dE"], P.get("dE_ld", 16), wr, eng.in_ch, P["H"] * eng.scale,
+                       P["W"] * eng.scale, charb_eps=charb_eps, loss_type=loss_type)
 
     def scatter_grad(self, eng, P, gE, inv):
         """An upstream dL/dE (NCHW fp32) times inv into the P['dE'] rows."""
@@ -321,9 +321,9 @@ class DirectTail(_OneConvTail):
         return H.epilogue(P["E"], mode=H.OUT_PSHUF_NCHW, ldo=0, bias=self.c.bp, ps=(eng.scale, Hh, Ww),
                           img=(eng.mean, eng.img_range, eng.in_ch, Hh, Ww))
 
-    def loss(self, eng, P, H_img, wr, charb_eps):
-        H.l1_loss(P["E"], H_img, P["loss"], P["dE"], self.c.Cop, wr, P["B"], eng.in_ch, P["H"] * eng.scale,
-                  P["W"] * eng.scale, P["loss_ws"], ps_r=eng.scale, charb_eps=charb_eps)
+    def loss(self, eng, P, H_img, wr, charb_eps, loss_type=None):
+        eng.pixel_loss(P, P["E"], H_img, P["dE"], self.c.Cop, wr, eng.in_ch, P["H"] * eng.scale, P["W"] * eng.scale,
+                       ps_r=eng.scale, charb_eps=charb_eps, loss_type=loss_type)
 
     def scatter_grad(self, eng, P, gE, inv):
         tmp = torch.nn.functional.pixel_unshuffle(gE.contiguous(), eng.scale)   # [B, C*r*r, H, W]

@@ -68,7 +68,7 @@ def segment_buckets(params, segs):
 class FusedTrainer:
     def __init__(self, netG, netE=None, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, E_decay=0.999,
                  loss_weight=1.0, use_graph=True, process_group=None, bucket_mb=25, segment_graphs=None, charb_eps=None,
-                 stream_priority=0):
+                 stream_priority=0, loss_type=None):
         self.net, self.ema_net = netG, netE
         self.stream_priority = stream_priority   # torch priority of the capture stream (0: default)
         self.device = next(netG.parameters()).device
@@ -90,6 +90,13 @@ class FusedTrainer:
         self.E_decay, self.loss_weight = E_decay, loss_weight
         # None: L1 (G_lossfn_type 'l1'); a float: the Charbonnier loss with that eps ('charbonnier')
         self.charb_eps = charb_eps
+        # loss_type None: charb_eps decides as above; 'ssim': weight * mean SSIM (kair_ssim_loss; the SSIM itself, so a
+        # run that maximises it has a negative loss_weight)
+        if loss_type not in (None, "l1", "charbonnier", "ssim"):
+            raise NotImplementedError(f"FusedTrainer: loss_type {loss_type!r}")
+        if loss_type == "charbonnier" and charb_eps is None:
+            raise ValueError("FusedTrainer: loss_type 'charbonnier' needs charb_eps")
+        self.loss_type = loss_type
         self.t = 0
         self.scal = torch.zeros(2, device=self.device)
         self.pg = process_group
@@ -138,7 +145,10 @@ class FusedTrainer:
             eng.forward(L, *cond)
         else:
             eng.forward(L, drop)
-        return eng.backward_from_loss(Hh, self.grads, self.loss_weight, charb_eps=self.charb_eps)
+        if self.loss_type == "ssim":
+            return eng.backward_from_loss(Hh, self.grads, self.loss_weight, loss_type="ssim")
+        return eng.backward_from_loss(Hh, self.grads, self.loss_weight,
+                                      charb_eps=None if self.loss_type == "l1" else self.charb_eps)
 
     def _update(self, loss=None):
         skip = None

@@ -148,11 +148,11 @@ class USRNetEngine(ResUNetProgram):
     # ------------------------------------------------------------------------------------
     # backward
     # ------------------------------------------------------------------------------------
-    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None):
+    def backward_from_loss(self, H_img, grads, loss_weight=1.0, charb_eps=None, loss_type=None):
         P = self.cur
-        H.l1_loss(P["it"][-1]["xout"], H_img, P["loss"], P["gE"], C8, loss_weight, P["B"], self.out_nc, P["H"], P["W"],
-                  P["loss_ws"], charb_eps=charb_eps)
-        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_nc * P["H"] * P["W"], loss_weight)
+        self.pixel_loss(P, P["it"][-1]["xout"], H_img, P["gE"], C8, loss_weight, self.out_nc, P["H"], P["W"],
+                        charb_eps=charb_eps, loss_type=loss_type)
+        P["e_g"] = self._x3_grad_exp(P["B"] * self.out_nc * P["H"] * P["W"], loss_weight, loss_type)
         self.backward(grads, P)
         return P["loss"]
 

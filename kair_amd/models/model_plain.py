@@ -98,6 +98,61 @@ class CharbonnierLoss(nn.Module):
         return torch.mean(torch.sqrt(d * d + self.eps))
 
 
+def _ssim_window(dtype, device):
+    """The 1-D factor of utils_image._gauss_window: exp(-x^2 / (2 * 1.5^2)) over 11 taps, sum 1 (float64)."""
+    x = torch.arange(11, dtype=torch.float64) - 5.0
+    g = torch.exp(-x * x / (2 * 1.5 * 1.5))
+    g = g / g.sum()
+    return torch.outer(g, g).to(device=device, dtype=dtype)
+
+
+class _SSIMKernel(torch.autograd.Function):
+    """mean SSIM of fp32 device images on kair_ssim_loss_nchw: the analytic gradient w.r.t. x comes with the value
+    (y, the target, gets none)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        from .. import _hip as H
+        B, C, Hh, Ww = x.shape
+        x, y = x.contiguous(), y.contiguous()
+        loss, g = torch.empty(1, device=x.device), torch.empty_like(x)
+        H.ssim_loss(x, y, loss, g, None, 1.0, B, C, Hh, Ww, H.ssim_workspace(B, C, Hh, Ww, x.device))
+        ctx.save_for_backward(g)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, go):
+        (g,) = ctx.saved_tensors
+        return g * go, None
+
+
+class SSIMLoss(nn.Module):
+    """G_lossfn_type 'ssim'.  The reference's models/loss_ssim.py is restated here from memory, not read: an 11 x 11
+    Gaussian window (sigma 1.5, sum 1; utils_image._gauss_window), depthwise filtering with zero padding 5 (borders
+    not renormalised), C1 = 0.01^2, C2 = 0.03^2 (data range 1),
+        S = (2 m1 m2 + C1)(2 s12 + C2) / ((m1^2 + m2^2 + C1)(s11 + s22 + C2)),
+    and the mean of S over B, C, H, W.  Like the reference module it returns the SSIM itself, not 1 - SSIM, and
+    ModelPlain multiplies it by G_lossfn_weight like every loss: a run that maximises SSIM sets a negative weight.
+
+    Plain torch (F.conv2d, groups = C; autograd backward) for CPU tensors and any dtype -- the tests' float64
+    reference; fp32 device tensors run kair_ssim_loss_nchw (value + analytic gradient w.r.t. x; y is the target)."""
+
+    def forward(self, x, y):
+        if x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and not y.requires_grad:
+            return _SSIMKernel.apply(x, y)
+        return self.ssim_map(x, y).mean()
+
+    @staticmethod
+    def ssim_map(x, y):
+        C = x.shape[1]
+        w = _ssim_window(x.dtype, x.device).expand(C, 1, 11, 11).contiguous()
+        f = lambda t: nn.functional.conv2d(t, w, padding=5, groups=C)
+        m1, m2 = f(x), f(y)
+        s11, s22, s12 = f(x * x) - m1 * m1, f(y * y) - m2 * m2, f(x * y) - m1 * m2
+        C1, C2 = 0.01 ** 2, 0.03 ** 2
+        return ((2 * m1 * m2 + C1) * (2 * s12 + C2)) / ((m1 * m1 + m2 * m2 + C1) * (s11 + s22 + C2))
+
+
 class ModelPlain(ModelBase):
     """Train with pixel loss."""
 
@@ -189,6 +244,8 @@ class ModelPlain(ModelBase):
             self.G_lossfn = nn.MSELoss(reduction="sum")
         elif t == "charbonnier":   # models/loss.py:208-218; the fused trainer runs kair_charbonnier_loss
             self.G_lossfn = CharbonnierLoss(self.opt_train.get("G_charbonnier_eps", 1e-9))
+        elif t == "ssim":   # the SSIM itself (maximised by a negative G_lossfn_weight); fused trainer: kair_ssim_loss
+            self.G_lossfn = SSIMLoss()
         else:
             raise NotImplementedError("Loss type [{:s}] is not on the kair_amd path.".format(t))
         self.G_lossfn_weight = self.opt_train["G_lossfn_weight"]
@@ -196,7 +253,7 @@ class ModelPlain(ModelBase):
     def _fused_ok(self):
         net = self.get_bare_model(self.netG)
         return (hasattr(net, "engine") and self.device.type == "cuda" and all(p.requires_grad for p in net.parameters())
-                and self.G_lossfn_type in ("l1", "charbonnier") and not self.opt_train.get("G_optimizer_clipgrad")
+                and self.G_lossfn_type in ("l1", "charbonnier", "ssim") and not self.opt_train.get("G_optimizer_clipgrad")
                 and self.opt_train["G_optimizer_type"] == "adam"
                 and not self.opt_train.get("G_regularizer_orthstep") and not self.opt_train.get("G_regularizer_clipstep"))
 
@@ -211,6 +268,7 @@ class ModelPlain(ModelBase):
                                         loss_weight=self.G_lossfn_weight,
                                         charb_eps=(tr.get("G_charbonnier_eps", 1e-9) if self.G_lossfn_type == "charbonnier"
                                                    else None),
+                                        loss_type="ssim" if self.G_lossfn_type == "ssim" else None,
                                         use_graph=tr.get("use_hip_graph", True))
             self.G_optimizer = FusedAdam(self.trainer.params, self.trainer, tr["G_optimizer_lr"],
                                          tr["G_optimizer_betas"], 1e-8, tr["G_optimizer_wd"])
