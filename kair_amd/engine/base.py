@@ -9,7 +9,8 @@ An engine is the launch sequence of one network over preallocated HBM buffers ("
   blocks (objects with a drop-path rate .dp; empty without stochastic depth), drop_path_scales()
   x3, x3_backoff(), X3_AEXP / x3_gexp_off / x3_backoffs: the fp32x3 range guard
   seg_hook, and grad_segments() where the engine reports gradient segments (data-parallel buckets)
-EngineBase holds all of it but the three launch sequences; ConvEngineBase adds the conv-net helpers.
+EngineBase holds all of it but the three launch sequences, and the GEMM launch layer they are written in (_nt, _wgrad:
+the fp32x3 operand exponents are set there and nowhere else); ConvEngineBase adds the conv-net helpers.
 """
 import math
 import weakref
@@ -190,6 +191,48 @@ class EngineBase:
         if self.seg_hook is not None:
             self.seg_hook()
 
+    # ---- the GEMM launch layer: kair_gemm_nt / kair_gemm_tn in the engine's arithmetic --------
+    @property
+    def tn_cd(self):
+        """The compute enum of kair_gemm_tn (the weight gradients): `cd`, under fp32x3 KAIR_COMPUTE_X3."""
+        return H.X3 if self.x3 else self.cd
+
+    def _nt(self, A, B, E, M, N, K):
+        """kair_gemm_nt in `cd`; under fp32x3 the split-fp16 arithmetic (compute KAIR_COMPUTE_X3): A is fp32 (split in
+        the kernel) or an fp16 pair (its lo plane attached with H.with_lo) carrying the phase exponent `_ax` (forward
+        the activation exponent, backward the gradient exponent), B a split-packed fp16 weight (2^KAIR_X3_WEXP), an
+        fp16 output the pair of v 2^(phase exponent)."""
+        if not self.x3:
+            H.gemm_nt(A, B, E, M, N, K, self.cd)
+            return
+        if A.dtype == H.F16 and not A.lo_ptr:
+            raise RuntimeError("fp32x3: an fp16 GEMM operand needs its lo plane")
+        if A.ones_col >= 0:
+            raise RuntimeError("fp32x3: no injected ones column on a GEMM A operand")
+        A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
+        if E.out_dtype == H.F16:
+            E.x3_out_exp = self._ax
+        H.gemm_nt(A, B, E, M, N, K, H.X3)
+
+    def _wgrad(self, P, A, Bop, M, N, K, wmap, grad, bgrad=None, ones_col=-1, ws=None, max_ctas=0, acc=False,
+               act_rows=False):
+        """One weight gradient A^T Bop over M rows: kair_gemm_tn into split partial planes (workspace ws, default
+        P["wg_ws"]), then the deterministic kair_wgrad_finalize into `grad` in the layout of wmap (added to it with
+        acc; bgrad: the bias gradient from the operand's ones column ones_col).  max_ctas > 0: at most that many
+        (tile, split) workgroups; < 0: -max_ctas times the splits.  fp32x3: (gradient, activation) operands, or
+        (activation, gradient) with act_rows (the transposed conv)."""
+        S = H.wgrad_splits(M, N, K)
+        if max_ctas > 0:   # fewer row splits
+            S = max(1, min(S, max_ctas // H.wgrad_tiles(N, K)))
+        elif max_ctas < 0:   # more, shorter ones (>= 32 rows each)
+            S = min(S * -max_ctas, -(-M // 32))
+        if self.x3:
+            eg, ea = P.get("e_g", 0), self.X3_AEXP
+            A.x3_exp, Bop.x3_exp = (ea, eg) if act_rows else (eg, ea)
+        ws = P["wg_ws"] if ws is None else ws
+        H.gemm_tn(A, Bop, ws, S, M, N, K, self.tn_cd)
+        H.wgrad_finalize(ws, S, wmap, grad, bgrad, ones_col, accumulate=acc)
+
     # ---- fp32x3 exponents and the range guard's reaction --------------------------------------
     def _x3_grad_exp(self, numel, weight=1.0, loss_type=None):
         """The fp32x3 gradient exponent: the mean-loss gradient is O(weight / numel) per output element (weight: the
@@ -227,6 +270,12 @@ class EngineBase:
         """The gradient exponent for an arbitrary upstream gradient of largest magnitude mx: max -> <= 2^8."""
         return 8 - int(math.ceil(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 0
 
+    def _x3_set_grad_exp(self, P, gE, scale=1.0, e_off=0):
+        """backward_from_grad under fp32x3: P["e_g"] from the range of the upstream gradient scale * gE itself (one
+        host sync; none off fp32x3), shifted by e_off."""
+        if self.x3:
+            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()) * scale) + e_off
+
     def x3_backoff(self, step=None, act=True, grad=True):
         """Range guard reaction (kair_range_check saw an inf / NaN the split operands can cause): lower the activation
         exponent (act: a forward overflow, the loss went non-finite) and / or the gradient exponent (grad: a backward
@@ -250,32 +299,17 @@ class EngineBase:
 
 
 class ConvEngineBase(EngineBase):
-    """Shared plumbing of the conv-net step programs: GEMM launch in the engine's arithmetic, conv weight-gradient
-    helpers.  fp32x3: cd stays F32 for the fp32-rows bookkeeping (gate_cast), the launches go through _nt /
-    conv_wgrad with compute KAIR_COMPUTE_X3."""
+    """Shared plumbing of the conv-net step programs: the conv weight-gradient helpers.  fp32x3: cd stays F32 for the
+    fp32-rows bookkeeping (gate_cast), the launches go through _nt / _wgrad with compute KAIR_COMPUTE_X3."""
 
     def __init__(self, net, compute_dtype):
         super().__init__(net, compute_dtype)
         self.cd = H.BF16 if compute_dtype == "bf16" else H.F32
 
-    def _nt(self, A, B, E, M, N, K):
-        """kair_gemm_nt in the engine's arithmetic; fp32x3: A carries the phase exponent, B the weight packs'."""
-        if self.x3:
-            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
-            H.gemm_nt(A, B, E, M, N, K, H.X3)
-        else:
-            H.gemm_nt(A, B, E, M, N, K, self.cd)
-
     def conv_wgrad(self, P, c, dz, ld_dz, src_op, M, grads, bias_src=None, ld_bias=None):
         """weight + bias gradient of conv c: dz [M, Cop] rows (compute dtype), src_op its im2col input;
         bias_src: the fp32 rows dz was cast from (bias gradient summed before rounding)."""
-        K = 9 * c.Cip
-        S = H.wgrad_splits(M, c.Cop, K)
-        A = H.rows(dz, ld=ld_dz)
-        if self.x3:   # (gradient, activation) operands
-            A.x3_exp, src_op.x3_exp = P["e_g"], self.X3_AEXP
-        H.gemm_tn(A, src_op, P["wg_ws"], S, M, c.Cop, K, H.X3 if self.x3 else self.cd)
-        H.wgrad_finalize(P["wg_ws"], S, c.map, grads[c.w])
+        self._wgrad(P, H.rows(dz, ld=ld_dz), src_op, M, c.Cop, 9 * c.Cip, c.map, grads[c.w])
         if bias_src is None:
             bias_src, ld_bias = dz, ld_dz
         H.colsum(H.rows(bias_src, ld=ld_bias), M, c.Cop, c.mapb, grads[c.b], P["colsum_ws"])
@@ -321,12 +355,13 @@ def lease_grads(ctx, gE):
 
 
 class ConvNetFunction(torch.autograd.Function):
-    """A whole conv network (RRDBNet / DnCNN / ...) as one autograd node on its step program; the
+    """A whole conv network (RRDBNet / DnCNN / FFDNet / DRUNet / USRNet) as one autograd node on its step program; the
     node leases its plan from forward to backward (kair_amd/engine/plans.py)."""
 
     @classmethod
     def run(cls, engine, x, params, *cond):
-        """cond: extra, non-differentiable forward inputs handed to engine.forward after x (FFDNet: sigma)."""
+        """cond: extra, non-differentiable forward inputs handed to engine.forward after x (FFDNet: sigma; USRNet: k,
+        sf, sigma)."""
         return cls.apply(engine, autograd_mode(params), len(cond), x, *cond, *params)
 
     @staticmethod

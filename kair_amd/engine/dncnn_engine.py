@@ -21,7 +21,7 @@ from .base import ConvEngineBase, _Conv, _rup
 
 
 class DnCNNEngine(ConvEngineBase):
-    COMPUTE_DTYPES = ("bf16", "fp32")   # (its GEMMs are launched in cd directly: no fp32x3 form)
+    COMPUTE_DTYPES = ("bf16", "fp32")
 
     def __init__(self, net, compute_dtype="bf16", residual=True):
         super().__init__(net, compute_dtype)
@@ -109,7 +109,7 @@ class DnCNNEngine(ConvEngineBase):
         B, _, h, w = x.shape
         P = self.plan(B, h, w)
         self.pack()
-        cd, nc = self.cd, self.nc
+        nc = self.nc
         M, Hh, Ww = P["M"], P["H"], P["W"]
         x = x.contiguous()
         self.cur = P
@@ -120,19 +120,19 @@ class DnCNNEngine(ConvEngineBase):
         for li, (c, bn, act, slope) in enumerate(self.layers[:-1]):
             a = P["a"][li]
             if bn is None:
-                H.gemm_nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(),
-                          H.epilogue(a, bias=c.bp, act=(H.ACT_RELU if act == 1 else H.ACT_LEAKY) if act else H.ACT_NONE,
-                                     slope=slope), M, nc, 9 * c.Cip, cd)
+                self._nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(),
+                         H.epilogue(a, bias=c.bp, act=(H.ACT_RELU if act == 1 else H.ACT_LEAKY) if act else H.ACT_NONE,
+                                    slope=slope), M, nc, 9 * c.Cip)
             else:
                 z = P["z"][li]
-                H.gemm_nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(), H.epilogue(z, bias=c.bp), M, nc, 9 * c.Cip, cd)
+                self._nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(), H.epilogue(z, bias=c.bp), M, nc, 9 * c.Cip)
                 H.bn_fwd(z, nc, a, nc, M, nc, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
                          training, P["mean"][li], P["rstd"][li], act, slope, P["bn_ws"])
                 if training:
                     bn.num_batches_tracked.add_(1)
             src, ldsrc, Cs = a, nc, nc
         c = self.layers[-1][0]
-        H.gemm_nt(H.im2col(src, Hh, Ww, nc), c.fwd(), self._out_epilogue(P, c), M, c.Cop, 9 * nc, cd)
+        self._nt(H.im2col(src, Hh, Ww, nc), c.fwd(), self._out_epilogue(P, c), M, c.Cop, 9 * nc)
         if self.residual:
             H.axpby(P["E"], x, 1.0, -1.0)     # x - model(x)
         return P["E"]
@@ -155,7 +155,7 @@ class DnCNNEngine(ConvEngineBase):
         H.act_grad_cast(P["dEf"], 16, None, 0, P["dn"], 16, M, 16, 0, 0.0, -1.0 if self.residual else 1.0)
         c = self.layers[-1][0]
         G = P["G"]
-        H.gemm_nt(H.im2col(P["dn"], Hh, Ww, 16, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * 16, cd)
+        self._nt(H.im2col(P["dn"], Hh, Ww, 16, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * 16)
         self.conv_wgrad(P, c, P["dn"], 16, H.im2col(P["a"][-1], Hh, Ww, nc), M, grads)
         for li in range(len(self.layers) - 2, -1, -1):
             c, bn, act, slope = self.layers[li]
@@ -170,7 +170,7 @@ class DnCNNEngine(ConvEngineBase):
             else:
                 bs = self.gate_cast(P, G, nc, a, nc, dz, nc, M, nc, act, slope)
             if li > 0:
-                H.gemm_nt(H.im2col(dz, Hh, Ww, nc, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * nc, cd)
+                self._nt(H.im2col(dz, Hh, Ww, nc, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * nc)
                 self.conv_wgrad(P, c, dz, nc, H.im2col(P["a"][li - 1], Hh, Ww, nc), M, grads, *bs)
             else:
                 self.conv_wgrad(P, c, dz, nc, H.im2col(P["xin"], Hh, Ww, self.Cin_p), M, grads, *bs)

@@ -68,8 +68,7 @@ class DRUNetEngine(ResUNetProgram):
     def backward_from_grad(self, gE, grads):
         P = self.cur
         H.image_to_nhwc(gE.contiguous(), P["gE"], C8, None, 1.0, P["B"], self.out_nc, P["H"], P["W"])
-        if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()))
+        self._x3_set_grad_exp(P, gE)
         self.backward(grads, P)
 
     def backward(self, grads, P):

@@ -6,7 +6,7 @@ the input shape.  Three kinds of users exist:
 * the fused trainer (FusedTrainer) runs forward + backward back to back and captures them in a HIP
   graph: it always gets the ``primary`` plan of its shape, so the captured pointers stay valid; no
   lease ever hands that plan out (a graph replay would overwrite a leased node's activations);
-* an autograd node (SwinIRFunction / ConvNetFunction / USRNetFunction) keeps the forward's saved
+* an autograd node (SwinIRFunction, or ConvNetFunction for every conv program) keeps the forward's saved
   activations until its backward: it ``lease``s a training plan, and a second forward of the same
   shape before that backward gets another plan instead of overwriting the first one's activations
   (gradient accumulation, two losses on two forwards).  The lease ends at backward, or when the

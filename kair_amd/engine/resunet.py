@@ -214,15 +214,6 @@ class ResUNetProgram(ConvEngineBase):
                  9 * nc[0])
 
     # ---- backward -------------------------------------------------------------------------
-    def _wgrad(self, P, A, Bop, M, N, K, m, grad, acc, act_rows=False):
-        """fp32x3: (gradient, activation) operands, or (activation, gradient) with act_rows (the transposed conv)."""
-        S = H.wgrad_splits(M, N, K)
-        if self.x3:
-            eg, ea = P.get("e_g", 0), self.X3_AEXP
-            A.x3_exp, Bop.x3_exp = (ea, eg) if act_rows else (eg, ea)
-        H.gemm_tn(A, Bop, P["wg_ws"], S, M, N, K, H.X3 if self.x3 else self.cd)
-        H.wgrad_finalize(P["wg_ws"], S, m, grad, accumulate=acc)
-
     def _chain_bwd(self, P, rbs, bufs, x_in, g, Hl, Wl, M, c, G, grads, acc, skip_g=None):
         """g: fp32 dL/d(chain output) -> returns fp32 dL/d(chain input) (+ skip_g, the U-Net skip)."""
         cur = g
@@ -231,11 +222,11 @@ class ResUNetProgram(ConvEngineBase):
             r_in = bufs[j - 1]["out"] if j > 0 else x_in
             self._nt(H.im2col(cur, Hl, Wl, c, flip=True), H.rows(rb.c2.Wd), H.epilogue(G["gz"], gate=S["h"], gate_kind=3),
                      M, c, 9 * c)
-            self._wgrad(P, H.rows(cur), H.im2col(S["h"], Hl, Wl, c), M, c, 9 * c, rb.c2.map, grads[rb.c2.w], acc)
+            self._wgrad(P, H.rows(cur), H.im2col(S["h"], Hl, Wl, c), M, c, 9 * c, rb.c2.map, grads[rb.c2.w], acc=acc)
             out = G["ga"] if cur is not G["ga"] else G["gb"]
             self._nt(H.im2col(G["gz"], Hl, Wl, c, flip=True), H.rows(rb.c1.Wd),
                      H.epilogue(out, resid=cur, resid2=skip_g if j == 0 else None), M, c, 9 * c)
-            self._wgrad(P, H.rows(G["gz"]), H.im2col(r_in, Hl, Wl, c), M, c, 9 * c, rb.c1.map, grads[rb.c1.w], acc)
+            self._wgrad(P, H.rows(G["gz"]), H.im2col(r_in, Hl, Wl, c), M, c, 9 * c, rb.c1.map, grads[rb.c1.w], acc=acc)
             cur = out
         return cur
 
@@ -249,7 +240,7 @@ class ResUNetProgram(ConvEngineBase):
                  9 * C8)
         s1 = S["up"][0][-1]["out"]
         self._wgrad(P, H.rows(gE), H.im2col(s1, H0, W0, nc[0]), M[0], C8, 9 * nc[0], self.tail.map, grads[self.tail.w],
-                    acc)
+                    acc=acc)
         g = Gs[0]["gS"]
         for u in (2, 1, 0):                        # m_up1, m_up2, m_up3
             l = 2 - u
@@ -261,7 +252,7 @@ class ResUNetProgram(ConvEngineBase):
             self._nt(H.s2d(gt, Hs, Ws, nc[l]), H.rows(up.Wd), H.epilogue(Gs[l + 1]["gS"]), M[l + 1], nc[l + 1],
                      4 * nc[l])
             self._wgrad(P, H.rows(s_next), H.s2d(gt, Hs, Ws, nc[l]), M[l + 1], nc[l + 1], 4 * nc[l], up.map,
-                        grads[up.w], acc, act_rows=True)
+                        grads[up.w], acc=acc, act_rows=True)
             g = Gs[l + 1]["gS"]
         H3, W3 = self._grid(P, 3)
         gx = self._chain_bwd(P, self.body_rbs, S["body"], S["X"][3], Gs[3]["gS"], H3, W3, M[3], nc[3], Gs[3], grads, acc,
@@ -273,11 +264,11 @@ class ResUNetProgram(ConvEngineBase):
             a = S["down"][l][-1]["out"]
             self._nt(H.rows(gx), H.rows(d.Wd), H.epilogue(Gs[l]["gc"], mode=H.OUT_PSHUF, ldo=nc[l], ps=(2, Hn, Wn)),
                      M[l + 1], 4 * nc[l], nc[l + 1])
-            self._wgrad(P, H.rows(gx), H.s2d(a, Hn, Wn, nc[l]), M[l + 1], nc[l + 1], 4 * nc[l], d.map, grads[d.w], acc)
+            self._wgrad(P, H.rows(gx), H.s2d(a, Hn, Wn, nc[l]), M[l + 1], nc[l + 1], 4 * nc[l], d.map, grads[d.w], acc=acc)
             gx = self._chain_bwd(P, self.down_rbs[l], S["down"][l], S["X"][l], Gs[l]["gc"], Hl, Wl, M[l], nc[l], Gs[l],
                                  grads, acc, skip_g=Gs[l]["gS"])
         if gxin is not None:
             self._nt(H.im2col(gx, H0, W0, nc[0], flip=True), H.rows(self.head.Wd), H.epilogue(gxin), M[0], C8,
                      9 * nc[0])
         self._wgrad(P, H.rows(gx), H.im2col(xin, H0, W0, C8), M[0], nc[0], 9 * C8, self.head.map,
-                    grads[self.head.w], acc)
+                    grads[self.head.w], acc=acc)

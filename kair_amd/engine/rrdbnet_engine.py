@@ -124,7 +124,7 @@ class RRDBNetEngine(ConvEngineBase):
         B, _, Hh, Ww = x.shape
         P = self.plan(B, Hh, Ww)
         self.pack()
-        cd, nf, gc, CD = self.cd, self.nf, self.gc, self.CD
+        nf, gc, CD = self.nf, self.gc, self.CD
         M = P["M"]
         x = x.contiguous()
         self.cur = P
@@ -185,12 +185,11 @@ class RRDBNetEngine(ConvEngineBase):
         P = self.cur
         HL, WL = P["levels"][-1]
         H.image_to_nhwc(gE.contiguous(), P["dE"], 16, None, 1.0, P["B"], self.out_ch, HL, WL)
-        if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()))
+        self._x3_set_grad_exp(P, gE)
         self.backward(grads, P)
 
     def backward(self, grads, P):
-        cd, nf, gc, CD = self.cd, self.nf, self.gc, self.CD
+        nf, CD = self.nf, self.CD
         self._ax = P.get("e_g", 0)   # fp32x3: backward GEMM A operands are data gradients
         B, Hh, Ww, M, ML = P["B"], P["H"], P["W"], P["M"], P["ML"]
         HL, WL = P["levels"][-1]
@@ -241,7 +240,7 @@ class RRDBNetEngine(ConvEngineBase):
 
     def _rdb_bwd(self, P, r, grads):
         """gy = dL/dy (y = x + 0.2 conv5(...)) -> replaced by dL/dx."""
-        cd, nf, gc, CD = self.cd, self.nf, self.gc, self.CD
+        nf, gc, CD = self.nf, self.gc, self.CD
         Hh, Ww, M = P["H"], P["W"], P["M"]
         cs, D, Gd, gy = self.rdbs[r], P["dense"][r], P["Gd"], P["gy"]
         c = cs[4]

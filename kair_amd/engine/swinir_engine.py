@@ -193,7 +193,6 @@ class SwinIREngine(EngineBase):
         # fp32x3 (EngineBase): operands fp32 (split inside the kernels) or fp16 hi/lo planes; the unfused launch
         # sequence of the fp32 engine
         self.cd = H.BF16 if compute_dtype in ("bf16", "fp32x3") else H.F32
-        self.tn_cd = H.X3 if self.x3 else self.cd   # kair_gemm_tn compute of the weight gradients
         self.split_conv = bool(split_conv) and compute_dtype == "bf16"
         # split activations only pay with split weights (a bf16 weight rounding dominates otherwise), and
         # the tied pair forms need split weight packs
@@ -497,9 +496,7 @@ class SwinIREngine(EngineBase):
         B, _, Hh, Ww = x.shape
         P = self.plan(B, Hh, Ww)
         self.pack()
-        cd, T = self.cd, self.tdt
-        M, Cp, nh = P["M"], self.Cp, self.nh
-        HW = Hh * Ww
+        M, Cp = P["M"], self.Cp
         x = x.contiguous()
         self.cur = P
         self._ax = self.X3_AEXP   # fp32x3: forward operands are activations
@@ -511,7 +508,7 @@ class SwinIREngine(EngineBase):
             H.image_to_nhwc(x, P["xin"], self.Cin_p, self.mean, self.img_range, B, self.in_ch, Hh, Ww)
         c = self.conv_first
         self._nt(H.im2col(P["xin"], Hh, Ww, self.Cin_p), c.fwd(), H.epilogue(P["f0"], bias=c.bp), M, Cp,
-                  9 * self.Cin_p, cd)
+                  9 * self.Cin_p)
         n = self.pe_norm
         H.layernorm_fwd(P["f0"], Cp, P["s0"], Cp, n.weight, n.bias, P["pe_mean"], P["pe_rstd"], M, self.C, n.eps)
         cur = P["s0"]
@@ -531,7 +528,7 @@ class SwinIREngine(EngineBase):
 
     def _resi_fwd(self, r, P, src, out, resid):
         """out = resi_conv(src) + resid (fp32 token rows, Cp columns)."""
-        cd, Cp, M, Hh, Ww = self.cd, self.Cp, P["M"], P["H"], P["W"]
+        Cp, M, Hh, Ww = self.Cp, P["M"], P["H"], P["W"]
         if not isinstance(r, _Resi3):
             # training: the halo conv also leaves the bf16 weight-gradient operand (1.0 in channel C)
             ac = (P["conv_bf"][id(r)][1], self.C) if P.get("conv_halo") else None
@@ -544,19 +541,19 @@ class SwinIREngine(EngineBase):
                              split=True)
                 return
             self._nt(self._ain(H.im2col(src, Hh, Ww, Cp)), r.fwd(), H.epilogue(out, bias=r.bp, resid=resid, acopy=ac), M,
-                      Cp, 9 * Cp, cd)
+                      Cp, 9 * Cp)
             return
         t1, t2 = P["r3"][id(r)]
         lk = dict(act=H.ACT_LEAKY, slope=0.2)
-        self._nt(H.im2col(src, Hh, Ww, Cp), r.c1.fwd(), H.epilogue(t1, bias=r.c1.bp, **lk), M, r.Cq, 9 * Cp, cd)
-        self._nt(H.rows(t1), H.rows(r.c2.Wp), H.epilogue(t2, bias=r.c2.bp, **lk), M, r.Cq, r.Cq, cd)
-        self._nt(H.im2col(t2, Hh, Ww, r.Cq), r.c3.fwd(), H.epilogue(out, bias=r.c3.bp, resid=resid), M, Cp, 9 * r.Cq, cd)
+        self._nt(H.im2col(src, Hh, Ww, Cp), r.c1.fwd(), H.epilogue(t1, bias=r.c1.bp, **lk), M, r.Cq, 9 * Cp)
+        self._nt(H.rows(t1), H.rows(r.c2.Wp), H.epilogue(t2, bias=r.c2.bp, **lk), M, r.Cq, r.Cq)
+        self._nt(H.im2col(t2, Hh, Ww, r.Cq), r.c3.fwd(), H.epilogue(out, bias=r.c3.bp, resid=resid), M, Cp, 9 * r.Cq)
 
     def _resi_bwd(self, r, P, G, src, D, grads):
         """resi_conv backward for out = resi_conv(src) + resid: G = dL/d out (fp32 rows) -> D = dL/d src
         (the conv path only; the caller adds the skip).  '1conv' returns its weight-gradient job for
         the deferred per-RSTB work; '3conv' issues its weight gradients here."""
-        cd, Cp, M, Hh, Ww = self.cd, self.Cp, P["M"], P["H"], P["W"]
+        Cp, M, Hh, Ww = self.Cp, P["M"], P["H"], P["W"]
         g = lambda p: grads[p]
         if not isinstance(r, _Resi3):
             ac = (P["conv_bf"][id(r)][0], -1) if P.get("conv_halo") else None
@@ -565,7 +562,7 @@ class SwinIREngine(EngineBase):
             elif P.get("conv_wr") and r.wr:
                 H.conv3x3_wr(G, Cp, 1, r.Wd16, None, None, D, P["B"], Hh, Ww, Cp, Cp, acopy=ac[0], split=False)
             else:
-                self._nt(H.im2col(G, Hh, Ww, Cp, flip=True), H.rows(r.Wd), H.epilogue(D, acopy=ac), M, Cp, 9 * Cp, cd)
+                self._nt(H.im2col(G, Hh, Ww, Cp, flip=True), H.rows(r.Wd), H.epilogue(D, acopy=ac), M, Cp, 9 * Cp)
             if self.conv_tap:   # bf16 operands: the halo convs' copies (else taken when the job runs)
                 return ("tap", G, src, r, g(r.w), g(r.b))
             return (H.rows(G), H.im2col(src, Hh, Ww, Cp, ones_col=self.C), M, Cp, 9 * Cp, r.map, g(r.w), g(r.b), self.C)
@@ -575,15 +572,15 @@ class SwinIREngine(EngineBase):
         # 3x3 Cq -> C: dL/d t2, gated by LeakyReLU'(t2 pre-activation)
         dz2 = P["r3_dz"][0].view(-1)[:M * q].view(M, q)
         dz1 = P["r3_dz"][1].view(-1)[:M * q].view(M, q)
-        self._nt(H.im2col(G, Hh, Ww, Cp, flip=True), H.rows(r.c3.Wd), H.epilogue(dz2, gate=t2, **lk), M, q, 9 * Cp, cd)
+        self._nt(H.im2col(G, Hh, Ww, Cp, flip=True), H.rows(r.c3.Wd), H.epilogue(dz2, gate=t2, **lk), M, q, 9 * Cp)
         self._wgrad(P, H.rows(G), H.im2col(t2, Hh, Ww, q), M, Cp, 9 * q, r.c3.map, g(r.c3.w))
         self._bias_colsum(P, H.rows(G), M, Cp, r.c3.mapb, g(r.c3.b))
         # 1x1 Cq -> Cq
-        self._nt(H.rows(dz2), H.rows(r.c2.Wt), H.epilogue(dz1, gate=t1, **lk), M, q, q, cd)
+        self._nt(H.rows(dz2), H.rows(r.c2.Wt), H.epilogue(dz1, gate=t1, **lk), M, q, q)
         self._wgrad(P, H.rows(dz2), H.rows(t1), M, q, q, r.c2.map, g(r.c2.w))
         self._bias_colsum(P, H.rows(dz2), M, q, r.c2.mapb, g(r.c2.b))
         # 3x3 C -> Cq
-        self._nt(H.im2col(dz1, Hh, Ww, q, flip=True), H.rows(r.c1.Wd), H.epilogue(D), M, Cp, 9 * q, cd)
+        self._nt(H.im2col(dz1, Hh, Ww, q, flip=True), H.rows(r.c1.Wd), H.epilogue(D), M, Cp, 9 * q)
         self._wgrad(P, H.rows(dz1), H.im2col(src, Hh, Ww, Cp), M, q, 9 * Cp, r.c1.map, g(r.c1.w))
         self._bias_colsum(P, H.rows(dz1), M, q, r.c1.mapb, g(r.c1.b))
         return None
@@ -606,25 +603,43 @@ class SwinIREngine(EngineBase):
         A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
         H.gemm_nt_lnbwd(A, B, M, self.Cp, K, x, self.Cp, gamma, mean, rstd, self.C, D, self.Cp, part, win=win, copy=copy)
 
-    def _nt(self, A, B, E, M, N, K, cd):
-        """kair_gemm_nt; under fp32x3 the split-fp16 arithmetic (compute KAIR_COMPUTE_X3): A is fp32 (split in the
-        kernel) or an fp16 pair (its lo plane attached with H.with_lo) carrying the phase exponent (forward 0,
-        backward the gradient exponent), B a split-packed fp16 weight (2^KAIR_X3_WEXP), an fp16 output the
-        pair of v 2^(phase exponent)."""
+    @staticmethod
+    def _epi(t, **kw):
+        """_op's epilogue twin: the GEMM output t, an fp16 pair [2, ...] (fp32x3: hi plane + lo plane) or a plain
+        tensor."""
+        if t.dtype == torch.float16 and t.shape[0] == 2:
+            return H.epilogue(t[0], out_lo=t[1], **kw)
+        return H.epilogue(t, **kw)
+
+    # The kernels with an fp32x3 twin, picked by the engine's arithmetic.  fp32x3: the operands are fp16 pairs of
+    # v 2^exponent (activations X3_AEXP, gradients P["e_g"]) and the head pad self.hp is 32 (16 is a bf16 layout).
+    def _ln_fwd(self, x, y, n, mean, rstd, M, win=(0, 0, 0, 0)):
+        """LayerNorm n of the x rows into the GEMM operand y (win: window-ordered rows), 1.0 in its first pad column."""
+        args = (x, self.Cp, y, self.Cp, n.weight, n.bias, mean, rstd, M, self.C, n.eps, win)
         if self.x3:
-            if A.dtype == H.F16 and not A.lo_ptr:
-                raise RuntimeError("fp32x3: an fp16 GEMM operand needs its lo plane")
-            A.x3_exp, B.x3_exp = self._ax, H.X3_WEXP
-            if A.ones_col >= 0:
-                raise RuntimeError("fp32x3: no injected ones column on a GEMM A operand")
-            if E.out_dtype == H.F16:
-                E.x3_out_exp = self._ax
-            H.gemm_nt(A, B, E, M, N, K, H.X3)
-            return
-        H.gemm_nt(A, B, E, M, N, K, cd)
+            H.layernorm_fwd_x3(*args, one_col=self.C, x3_exp=self.X3_AEXP)
+        else:
+            H.layernorm_fwd(*args, one_col=self.C)
+
+    def _attn_fwd(self, blk, P, S):
+        nh, hd, hp = self.nh, self.C // self.nh, self.hp
+        args = (S["qkv"], blk.table, S["O"], nh * hp, S["lse"], P["nWin"], nh, hd, blk.scale, P["H"], P["W"], blk.shift)
+        if self.x3:   # q/k/v hi/lo planes in, O out as a pair too
+            H.window_attn_fwd_x3(*args, ones_col=hd, e_in=self.X3_AEXP, e_out=self.X3_AEXP, ws=self.ws)
+        else:
+            H.window_attn_fwd(*args, ones_col=hd, head_pad=hp, ws=self.ws)
+
+    def _attn_bwd(self, blk, P, S, W, rows):
+        """P["dO"] -> W["dqkv"] (rows: as token rows, the row GEMM's operand) and the bias-table partials W["attn_ws"]."""
+        nh, hd, hp = self.nh, self.C // self.nh, self.hp
+        args = (S["qkv"], S["O"], nh * hp, P["dO"], nh * hp, blk.table, S["lse"], W["dqkv"], None, False, W["attn_ws"],
+                P["nWin"], nh, hd, blk.scale, P["H"], P["W"], blk.shift)
+        if self.x3:   # q/k/v and dO as hi/lo planes, dq/dk/dv token rows [M][3 nh 32] as a pair
+            H.window_attn_bwd_x3(*args, e_act=self.X3_AEXP, e_grad=P["e_g"], win_ws=self.ws)
+        else:
+            H.window_attn_bwd(*args, dqkv_rows=rows, head_pad=hp, win_ws=self.ws)
 
     def _block_fwd(self, blk, P, S, x, bi):
-        cd = self.cd
         M, Cp, nh, hp, Hh, Ww = P["M"], self.Cp, self.nh, self.hp, P["H"], P["W"]
         HW = Hh * Ww
         win = (Hh, Ww, self.ws, blk.shift)
@@ -639,67 +654,32 @@ class SwinIREngine(EngineBase):
                             S["lse"], blk.proj.Wg, blk.proj.bp, s_attn, HW, S["mid"], Cp, P["nWin"], nh, Hh, Ww,
                             blk.shift, w_split=blk.qkv.split)
         else:
-            if self.x3:   # ln1 as the fp16 pair of its qkv / wgrad consumers
-                H.layernorm_fwd_x3(x, Cp, S["ln1"], Cp, blk.n1.weight, blk.n1.bias, S["m1"], S["r1"], M, self.C, blk.n1.eps,
-                                   win, one_col=self.C, x3_exp=self.X3_AEXP)
-            else:
-                H.layernorm_fwd(x, Cp, S["ln1"], Cp, blk.n1.weight, blk.n1.bias, S["m1"], S["r1"], M, self.C, blk.n1.eps,
-                                win, one_col=self.C)
+            self._ln_fwd(x, S["ln1"], blk.n1, S["m1"], S["r1"], M, win)
             l = blk.qkv
-            if self.x3:   # q/k/v as hi/lo planes into the split attention kernels, O out as a pair too
-                self._nt(self._op(S["ln1"]), H.rows(l.Wp), H.epilogue(S["qkv"][0], mode=H.OUT_QKVBLK, ldo=0, bias=l.bp,
-                                                                       qkv=(nh, 32, self.T), out_lo=S["qkv"][1]),
-                         M, l.Np, Cp, cd)
-                H.window_attn_fwd_x3(S["qkv"], blk.table, S["O"], nh * 32, S["lse"], P["nWin"], nh, self.C // nh, blk.scale,
-                                     Hh, Ww, blk.shift, ones_col=self.C // nh, e_in=self.X3_AEXP, e_out=self.X3_AEXP,
-                                     ws=self.ws)
-                A_o = self._op(S["O"])
-            else:
-                self._nt(H.rows(S["ln1"]), H.rows(l.Wp), H.epilogue(S["qkv"], mode=H.OUT_QKVBLK, ldo=0, bias=l.bp,
-                                                                     qkv=(nh, hp, self.T)), M, l.Np, Cp, cd)
-                H.window_attn_fwd(S["qkv"], blk.table, S["O"], nh * hp, S["lse"], P["nWin"], nh, self.C // nh, blk.scale,
-                                  Hh, Ww, blk.shift, ones_col=self.C // nh, head_pad=hp, ws=self.ws)
-                A_o = H.rows(S["O"])
+            self._nt(self._op(S["ln1"]), H.rows(l.Wp),
+                     self._epi(S["qkv"], mode=H.OUT_QKVBLK, ldo=0, bias=l.bp, qkv=(nh, hp, self.T)), M, l.Np, Cp)
+            self._attn_fwd(blk, P, S)
             l = blk.proj
-            self._nt(A_o, H.rows(l.Wp), H.epilogue(S["mid"], win=win, bias=l.bp, resid=x, rowscale=s_attn,
-                                                  rows_per_scale=HW), M, Cp, nh * hp, cd)
+            self._nt(self._op(S["O"]), H.rows(l.Wp), H.epilogue(S["mid"], win=win, bias=l.bp, resid=x, rowscale=s_attn,
+                                                                 rows_per_scale=HW), M, Cp, nh * hp)
         if self.fused_mlp:   # LN2 -> fc1 + GELU -> fc2 + residual in one launch
             f1, f2 = blk.fc1, blk.fc2
             H.swin_mlp_fwd(S["mid"], Cp, blk.n2.weight, blk.n2.bias, blk.n2.eps, self.C, S["ln2"], Cp, S["m2"], S["r2"],
                            f1.Wg, f1.bp, S["u"], S["h"], self.Hdp, f1.N, f2.Wg, f2.bp, s_mlp, HW, S["out"], Cp, M, Cp,
                            self.Hdp, w_split=f1.split)
             return S["out"]
-        if self.x3:
-            H.layernorm_fwd_x3(S["mid"], Cp, S["ln2"], Cp, blk.n2.weight, blk.n2.bias, S["m2"], S["r2"], M, self.C,
-                               blk.n2.eps, one_col=self.C, x3_exp=self.X3_AEXP)
-        else:
-            H.layernorm_fwd(S["mid"], Cp, S["ln2"], Cp, blk.n2.weight, blk.n2.bias, S["m2"], S["r2"], M, self.C, blk.n2.eps,
-                            one_col=self.C)
+        self._ln_fwd(S["mid"], S["ln2"], blk.n2, S["m2"], S["r2"], M)
         l = blk.fc1
-        hb = S["h"]
-        E1 = (H.epilogue(hb[0], out_lo=hb[1], bias=l.bp, act=H.ACT_GELU, pre=S["u"], ones_col=l.N, pre_grad=True)
-              if self.x3 else H.epilogue(hb, bias=l.bp, act=H.ACT_GELU, pre=S["u"], ones_col=l.N, pre_grad=True))
-        self._nt(self._op(S["ln2"]), H.rows(l.Wp), E1, M, l.Np, Cp, cd)
+        self._nt(self._op(S["ln2"]), H.rows(l.Wp),
+                 self._epi(S["h"], bias=l.bp, act=H.ACT_GELU, pre=S["u"], ones_col=l.N, pre_grad=True), M, l.Np, Cp)
         l = blk.fc2
         self._nt(self._op(S["h"]), H.rows(l.Wp), H.epilogue(S["out"], bias=l.bp, resid=S["mid"], rowscale=s_mlp,
-                                                              rows_per_scale=HW), M, Cp, self.Hdp, cd)
+                                                              rows_per_scale=HW), M, Cp, self.Hdp)
         return S["out"]
 
     # ------------------------------------------------------------------------------------
     # backward
     # ------------------------------------------------------------------------------------
-    def _wgrad(self, P, A, Bop, M, N, K, layer_map, wgrad, bgrad=None, ones_col=-1, ws=None, max_ctas=0):
-        S = H.wgrad_splits(M, N, K)
-        if self.x3:   # (gradient, activation) operands
-            A.x3_exp, Bop.x3_exp = P["e_g"], self.X3_AEXP
-        if max_ctas > 0:   # fewer row splits: at most max_ctas (tile, split) workgroups
-            S = max(1, min(S, max_ctas // H.wgrad_tiles(N, K)))
-        elif max_ctas < 0:   # more, shorter ones (-max_ctas times the splits, >= 32 rows each)
-            S = min(S * -max_ctas, -(-M // 32))
-        ws = P["wg_ws"] if ws is None else ws
-        H.gemm_tn(A, Bop, ws, S, M, N, K, self.tn_cd)
-        H.wgrad_finalize(ws, S, layer_map, wgrad, bgrad, ones_col)
-
     def _run_conv_job(self, P, job, ws=None, max_ctas=0):
         """A '1conv' residual conv's weight gradient (the job _resi_bwd returned).  Tap form: G and the
         conv input go to bf16 copies (the input with 1.0 in channel C for the bias), then one ring launch
@@ -748,8 +728,7 @@ class SwinIREngine(EngineBase):
         (the range guard's retry, SwinIRFunction.backward)."""
         P = self.cur
         inv = 1.0 / self.img_range   # E = v / img_range + ...
-        if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()) * inv) + e_off
+        self._x3_set_grad_exp(P, gE, inv, e_off)
         self.tail.scatter_grad(self, P, gE, inv)
         self.backward(grads, P)
 
@@ -877,8 +856,9 @@ class SwinIREngine(EngineBase):
         its RSTB; P["gw"][j] holds this block's weight-gradient operands until the RSTB's grouped
         launch.  On entry gw[j]["Dm"] = s_mlp * D (compute dtype, token order); LN2 backward writes
         gw[j]["Da"] = s_attn * D_mid (window order, proj operand); LN1 backward, when the previous block
-        is in the same RSTB, writes that block's gw[j - 1]["Dm"]."""
-        cd, g = self.cd, (lambda p: grads[p])
+        is in the same RSTB, writes that block's gw[j - 1]["Dm"].  fp32x3: the operands in gw, S and P["dO"] are fp16
+        pairs (_op / _epi), the kernels their split twins (_attn_bwd; _nt and _wg launch in KAIR_COMPUTE_X3)."""
+        g = lambda p: grads[p]
         M, Cp, nh, Hh, Ww = P["M"], self.Cp, self.nh, P["H"], P["W"]
         HW = Hh * Ww
         win = (Hh, Ww, self.ws, blk.shift)
@@ -904,9 +884,7 @@ class SwinIREngine(EngineBase):
             self._lnp_pending.append((W["ln2p"], M, self.C, g(n.weight), g(n.bias), False, P["rg_nb"][self.Hdp]))
         else:
             # S["u"] holds GELU'(fc1 pre-activation), stored by the forward (pre_grad): a plain multiply here
-            Eu = (H.epilogue(dU[0], out_lo=dU[1], gate=S["u"], gate_kind=4) if self.x3 else
-                  H.epilogue(dU, gate=S["u"], gate_kind=4))
-            self._nt(self._op(Dm), H.rows(fc2.Wt), Eu, M, self.Hdp, Cp, cd)
+            self._nt(self._op(Dm), H.rows(fc2.Wt), self._epi(dU, gate=S["u"], gate_kind=4), M, self.Hdp, Cp)
             cpy = H.copy_desc(Da, rowscale=s_attn, rows_per_scale=HW, win=win, x3_exp=P["e_g"])
             if self.x3_lnfuse:   # fc1 input gradient + LN2 backward in one launch
                 self._nt_lnbwd(self._op(dU), H.rows(fc1.Wt), M, self.Hdp, S["mid"], n.weight, S["m2"], S["r2"], D,
@@ -914,79 +892,48 @@ class SwinIREngine(EngineBase):
                 self._lnp_pending.append((W["ln2p"], M, self.C, g(n.weight), g(n.bias), False,
                                           H.gemm_nt_lnbwd_parts(M, Cp)))
             else:
-                self._nt(self._op(dU), H.rows(fc1.Wt), H.epilogue(P["dxn"]), M, Cp, self.Hdp, cd)
+                self._nt(self._op(dU), H.rows(fc1.Wt), H.epilogue(P["dxn"]), M, Cp, self.Hdp)
                 H.layernorm_bwd(S["mid"], Cp, P["dxn"], Cp, n.weight, S["m2"], S["r2"], D, Cp, True, None, None, False,
                                 W["ln2p"], M, self.C, copy=cpy)
                 self._lnp_pending.append((W["ln2p"], M, self.C, g(n.weight), g(n.bias), False))
         self._wg(P, self._op(dU), self._op(S["ln2"], ones_col=self.C, ones_in_data=True), self.Hdp, Cp, fc1, grads, self.C)
         # attention: mid = x + s_attn * proj(attn(LN1(x)))   (window order inside)
         proj, qkv = blk.proj, blk.qkv
-        if self.x3:
-            self._block_bwd_attn_x3(blk, P, S, x_in, D, bi, grads, j, par)
-            return
         hp = self.hp
-        self._wg(P, H.rows(Da), H.rows(S["O"], ones_col=hd, ones_in_data=True), Cp, nh * hp, proj, grads, hd)
+        self._wg(P, self._op(Da), self._op(S["O"], ones_col=hd, ones_in_data=True), Cp, nh * hp, proj, grads, hd)
         if self.rowgemm:
             H.rowgemm_store(Da, M, Cp, proj.Wgt, Cp, P["dO"])
         else:
-            self._nt(H.rows(Da), H.rows(proj.Wt), H.epilogue(P["dO"]), M, nh * hp, Cp, cd)
+            self._nt(self._op(Da), H.rows(proj.Wt), self._epi(P["dO"]), M, nh * hp, Cp)
         rows = self.rowgemm   # dq/dk/dv as token rows [M][3 nh 32]: the row GEMM's A operand
-        H.window_attn_bwd(S["qkv"], S["O"], nh * hp, P["dO"], nh * hp, blk.table, S["lse"], dqkv, None, False,
-                          W["attn_ws"], P["nWin"], nh, hd, blk.scale, Hh, Ww, blk.shift, dqkv_rows=rows, head_pad=hp,
-                          win_ws=self.ws)
-        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, self.cd, g(blk.table), False, self.ws))
-        A_qkv = H.rows(dqkv.view(M, qkv.Np)) if rows else H.qkvblk(dqkv, nh, hdp=hp, ws=self.ws)
-        self._wg(P, A_qkv, H.rows(S["ln1"], ones_col=self.C, ones_in_data=True), qkv.Np, Cp, qkv, grads, self.C)
-        n = blk.n1
-        cp = None
-        if j > 0:   # the previous block's MLP operand: s_mlp(prev) * dL/d x_in
-            cp = H.copy_desc(P["gw"][par][j - 1]["Dm"], rowscale=drop[bi - 1, 1] if drop is not None else None,
-                             rows_per_scale=HW)
-        if rows:
-            # q/k/v input gradient (rows in window order) -> LN1 backward into D (+ the previous block's operand)
-            H.rowgemm_lnbwd(dqkv.view(M, qkv.Np), M, qkv.Np, qkv.Wgt, x_in, n.weight, S["m1"], S["r1"], self.C, D,
-                            W["ln1p"], win=win, copy=cp)
-            self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False, P["rg_nb"][qkv.Np]))
+        self._attn_bwd(blk, P, S, W, rows)
+        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, self.tn_cd, g(blk.table), False, self.ws))
+        if self.x3:   # token rows too, as a pair
+            A_qkv = lambda: self._op(dqkv)
+        elif rows:
+            A_qkv = lambda: H.rows(dqkv.view(M, qkv.Np))
         else:
-            self._nt(H.qkvblk(dqkv, nh, hdp=hp, ws=self.ws), H.rows(qkv.Wt), H.epilogue(P["dxn"]), M, Cp, qkv.Np, cd)
-            H.layernorm_bwd(x_in, Cp, P["dxn"], Cp, n.weight, S["m1"], S["r1"], D, Cp, True, None, None, False,
-                            W["ln1p"], M, self.C, win, copy=cp)
-            self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False))
-
-
-    def _block_bwd_attn_x3(self, blk, P, S, x_in, D, bi, grads, j, par):
-        """The attention half of _block_bwd under fp32x3: q/k/v and dO as hi/lo fp16 planes, O and dq/dk/dv fp32, the
-        split attention backward, split GEMMs (kair_gemm_nt / kair_gemm_tn compute X3)."""
-        cd, g = self.cd, (lambda p: grads[p])
-        M, Cp, nh, Hh, Ww = P["M"], self.Cp, self.nh, P["H"], P["W"]
-        HW = Hh * Ww
-        win = (Hh, Ww, self.ws, blk.shift)
-        drop = P["drop"]
-        hd = self.C // nh
-        W = P["gw"][par][j]
-        Da, dqkv = W["Da"], W["dqkv"]
-        proj, qkv = blk.proj, blk.qkv
-        self._wg(P, self._op(Da), self._op(S["O"], ones_col=hd, ones_in_data=True), Cp, nh * 32, proj, grads, hd)
-        self._nt(self._op(Da), H.rows(proj.Wt), H.epilogue(P["dO"][0], out_lo=P["dO"][1]), M, nh * 32, Cp, cd)
-        H.window_attn_bwd_x3(S["qkv"], S["O"], nh * 32, P["dO"], nh * 32, blk.table, S["lse"], dqkv, None, False,
-                             W["attn_ws"], P["nWin"], nh, hd, blk.scale, Hh, Ww, blk.shift, e_act=self.X3_AEXP,
-                             e_grad=P["e_g"], win_ws=self.ws)
-        self._dtab_pending.append((W["attn_ws"], P["nWin"], nh, H.X3, g(blk.table), False, self.ws))
-        self._wg(P, self._op(dqkv), self._op(S["ln1"], ones_col=self.C, ones_in_data=True), qkv.Np, Cp, qkv, grads, self.C)
+            A_qkv = lambda: H.qkvblk(dqkv, nh, hdp=hp, ws=self.ws)
+        self._wg(P, A_qkv(), self._op(S["ln1"], ones_col=self.C, ones_in_data=True), qkv.Np, Cp, qkv, grads, self.C)
         n = blk.n1
         cp = None
         if j > 0:   # the previous block's MLP operand: s_mlp(prev) * dL/d x_in
             cp = H.copy_desc(P["gw"][par][j - 1]["Dm"], rowscale=drop[bi - 1, 1] if drop is not None else None,
                              rows_per_scale=HW, x3_exp=P["e_g"])
-        if self.x3_lnfuse:   # q/k/v input gradient + LN1 backward in one launch
-            self._nt_lnbwd(self._op(dqkv), H.rows(qkv.Wt), M, qkv.Np, x_in, n.weight, S["m1"], S["r1"], D, W["ln1p"],
+        if rows:
+            # q/k/v input gradient (rows in window order) -> LN1 backward into D (+ the previous block's operand)
+            H.rowgemm_lnbwd(dqkv.view(M, qkv.Np), M, qkv.Np, qkv.Wgt, x_in, n.weight, S["m1"], S["r1"], self.C, D,
+                            W["ln1p"], win=win, copy=cp)
+            self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False, P["rg_nb"][qkv.Np]))
+        elif self.x3_lnfuse:   # q/k/v input gradient + LN1 backward in one launch
+            self._nt_lnbwd(A_qkv(), H.rows(qkv.Wt), M, qkv.Np, x_in, n.weight, S["m1"], S["r1"], D, W["ln1p"],
                            win=win, copy=cp)
             self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False, H.gemm_nt_lnbwd_parts(M, Cp)))
-            return
-        self._nt(self._op(dqkv), H.rows(qkv.Wt), H.epilogue(P["dxn"]), M, Cp, qkv.Np, cd)
-        H.layernorm_bwd(x_in, Cp, P["dxn"], Cp, n.weight, S["m1"], S["r1"], D, Cp, True, None, None, False,
-                        W["ln1p"], M, self.C, win, copy=cp)
-        self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False))
+        else:
+            self._nt(A_qkv(), H.rows(qkv.Wt), H.epilogue(P["dxn"]), M, Cp, qkv.Np)
+            H.layernorm_bwd(x_in, Cp, P["dxn"], Cp, n.weight, S["m1"], S["r1"], D, Cp, True, None, None, False,
+                            W["ln1p"], M, self.C, win, copy=cp)
+            self._lnp_pending.append((W["ln1p"], M, self.C, g(n.weight), g(n.bias), False))
 
 
 class SwinIRFunction(torch.autograd.Function):

@@ -102,7 +102,7 @@ class PixelShuffleTail(_Tail):
         return [16] + [c.Co for c in self.ups]
 
     def forward(self, eng, P):
-        cd, Cp, M, B, Hh, Ww = eng.cd, eng.Cp, P["M"], P["B"], P["H"], P["W"]
+        Cp, M, B, Hh, Ww = eng.Cp, P["M"], P["B"], P["H"], P["W"]
         sa, tl = eng.split_act, P["tail_ld"]
         lo = (lambda t: t[:, NF:]) if sa else (lambda t: None)   # the lo half of a pair buffer
         c = self.cbu
@@ -112,7 +112,7 @@ class PixelShuffleTail(_Tail):
         else:
             eng._nt(eng._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(),
                     H.epilogue(P["a0"], ldo=tl, bias=c.bp, act=H.ACT_LEAKY, slope=0.01, out_lo=lo(P["a0"])), M, NF,
-                    9 * Cp, cd)
+                    9 * Cp)
         src, h, w = P["a0"], Hh, Ww
         for c, r, dst in zip(self.ups, self.ups_r, P["ups_act"]):
             if eng._wr_ok(c.wr_pair, 1, B, h, w, NF, c.Co):   # kair_conv3x3_wr, pair form
@@ -121,7 +121,7 @@ class PixelShuffleTail(_Tail):
             else:
                 A = H.asplit(H.im2col(src, h, w, c.fcip), pair=True) if sa else H.im2col(src, h, w, NF)
                 eng._nt(A, c.fwd(), H.epilogue(dst, mode=H.OUT_PSHUF_SPM, ldo=tl, bias=c.bp, ps=(r, h, w), out_lo=lo(dst)),
-                        B * h * w, c.Co, 9 * c.fcip, cd)
+                        B * h * w, c.Co, 9 * c.fcip)
             src, h, w = dst, h * r, w * r
         c = self.last
         if self.last_narrow_x3 and w % 64 == 0:
@@ -133,11 +133,11 @@ class PixelShuffleTail(_Tail):
         else:
             eng._nt(eng._ain(H.im2col(src, h, w, NF, ld=tl), lo(src)), c.fwd(),
                     H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(eng.mean, eng.img_range, eng.in_ch, h, w)),
-                    B * h * w, c.Cop, 9 * NF, cd)
+                    B * h * w, c.Cop, 9 * NF)
         return P["E"]
 
     def backward(self, eng, P, grads):
-        cd, Cp, M, B, Hh, Ww = eng.cd, eng.Cp, P["M"], P["B"], P["H"], P["W"]
+        Cp, M, B, Hh, Ww = eng.Cp, P["M"], P["B"], P["H"], P["W"]
         g = lambda p: grads[p]
         h, w = Hh, Ww
         for r in self.ups_r:
@@ -160,7 +160,7 @@ class PixelShuffleTail(_Tail):
             eng._nt(H.im2col(P["dE"], h, w, 16, flip=True), H.rows(c.Wd),
                     H.epilogue(P["dpre"][-1], mode=H.OUT_PUNSHUF_SPM, ldo=self.ups[-1].Co,
                                ps=(r_last, h // r_last, w // r_last)),
-                    B * h * w, NF, 9 * 16, cd)
+                    B * h * w, NF, 9 * 16)
             eng._wgrad(P, H.rows(P["dE"]), H.im2col(src, h, w, NF, ld=tl), B * h * w, 16, 9 * NF, c.map, g(c.w))
             eng._bias_colsum(P, H.rows(P["dE"]), B * h * w, 16, c.mapb, g(c.b))
         # upsampling convs, last to first
@@ -182,17 +182,17 @@ class PixelShuffleTail(_Tail):
                 eng._nt(H.im2col(dpre, h, w, c.Co, flip=True), H.rows(c.Wd),
                         H.epilogue(P["dpre"][i - 1], mode=H.OUT_PUNSHUF_SPM, ldo=self.ups[i - 1].Co,
                                    ps=(rp, h // rp, w // rp)),
-                        B * h * w, NF, 9 * c.Co, cd)
+                        B * h * w, NF, 9 * c.Co)
             else:
                 eng._nt(H.im2col(dpre, h, w, c.Co, flip=True), H.rows(c.Wd),
-                        H.epilogue(P["da0"], gate=P["a0"], ldg=tl, gate_kind=2, slope=0.01), M, NF, 9 * c.Co, cd)
+                        H.epilogue(P["da0"], gate=P["a0"], ldg=tl, gate_kind=2, slope=0.01), M, NF, 9 * c.Co)
             eng._wgrad(P, H.rows(dpre), H.im2col(src, h, w, NF, ld=tl), B * h * w, c.Co, 9 * NF, c.map, g(c.w))
             eng._bias_colsum(P, H.rows(dpre), B * h * w, c.Co, c.mapb, g(c.b))
         c = self.cbu
         if eng._wr_ok(c.wr_n64, 0, B, Hh, Ww, NF, Cp):
             H.conv3x3_wr(P["da0"], NF, 1, c.Wc16, None, None, P["dfb"], B, Hh, Ww, NF, Cp, split=False)
         else:
-            eng._nt(H.im2col(P["da0"], Hh, Ww, NF, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * NF, cd)
+            eng._nt(H.im2col(P["da0"], Hh, Ww, NF, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * NF)
         eng._wgrad(P, H.rows(P["da0"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=eng.C), M, NF, 9 * Cp, c.map,
                    g(c.w), g(c.b), eng.C)
 
@@ -232,34 +232,34 @@ class NearestConvTail(_Tail):
         return [self.last.Cop, self.hrc.Cop, NF]
 
     def forward(self, eng, P):
-        cd, Cp, M, B, h, w = eng.cd, eng.Cp, P["M"], P["B"], P["H"], P["W"]
+        Cp, M, B, h, w = eng.Cp, P["M"], P["B"], P["H"], P["W"]
         c = self.cbu
         eng._nt(H.im2col(P["fb"], h, w, Cp), c.fwd(),
-                H.epilogue(P["a0"], bias=c.bp, act=H.ACT_LEAKY, slope=0.01), M, NF, 9 * Cp, cd)
+                H.epilogue(P["a0"], bias=c.bp, act=H.ACT_LEAKY, slope=0.01), M, NF, 9 * Cp)
         src = P["a0"]
         # lrelu(conv(nearest x2)) twice -- im2col reads through the upsample -- then lrelu(conv_hr)
         for c, up, dst in zip(self.nup + [self.hrc], (2, 2, 1), P["nup_act"] + [P["nhr"]]):
             h, w = up * h, up * w
             eng._nt(H.im2col(src, h, w, NF, up=up), c.fwd(), H.epilogue(dst, bias=c.bp, act=H.ACT_LEAKY, slope=0.2),
-                    B * h * w, NF, 9 * NF, cd)
+                    B * h * w, NF, 9 * NF)
             src = dst
         c = self.last
         eng._nt(H.im2col(P["nhr"], h, w, NF), c.fwd(),
                 H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(eng.mean, eng.img_range, eng.in_ch, h, w)),
-                B * h * w, c.Cop, 9 * NF, cd)
+                B * h * w, c.Cop, 9 * NF)
         return P["E"]
 
     def backward(self, eng, P, grads):
         """Each input gradient gated by LeakyReLU' in the dgrad epilogue (conv_hr, conv_up2) or after the 2x2
         sum-pool that is nearest x2's adjoint (conv_up2 -> up1 -> cbu)."""
-        cd, B, Hh, Ww, M, Cp = eng.cd, P["B"], P["H"], P["W"], P["M"], eng.Cp
+        B, Hh, Ww, M, Cp = P["B"], P["H"], P["W"], P["M"], eng.Cp
         g = lambda p: grads[p]
         h, w = 4 * Hh, 4 * Ww
         ML = B * h * w
         # conv_last (16 padded outputs) then conv_hr: dz = the conv's output gradient, src its input activation
         for c, dz, src, dst in ((self.last, P["dE"], P["nhr"], P["dz_hr"]), (self.hrc, P["dz_hr"], P["nup_act"][1], P["dz_u"])):
             eng._nt(H.im2col(dz, h, w, c.Cop, flip=True), H.rows(c.Wd), H.epilogue(dst, gate=src, gate_kind=2, slope=0.2),
-                    ML, NF, 9 * c.Cop, cd)
+                    ML, NF, 9 * c.Cop)
             eng._wgrad(P, H.rows(dz), H.im2col(src, h, w, NF), ML, c.Cop, 9 * NF, c.map, g(c.w))
             eng._bias_colsum(P, H.rows(dz), ML, c.Cop, c.mapb, g(c.b))
         dz = P["dz_u"]
@@ -268,7 +268,7 @@ class NearestConvTail(_Tail):
             Mi = B * h * w
             src = P["nup_act"][0] if i == 1 else P["a0"]
             G_hi = P["G_hi"][:Mi]
-            eng._nt(H.im2col(dz, h, w, NF, flip=True), H.rows(c.Wd), H.epilogue(G_hi), Mi, NF, 9 * NF, cd)
+            eng._nt(H.im2col(dz, h, w, NF, flip=True), H.rows(c.Wd), H.epilogue(G_hi), Mi, NF, 9 * NF)
             eng._wgrad(P, H.rows(dz), H.im2col(src, h, w, NF, up=2), Mi, NF, 9 * NF, c.map, g(c.w))
             eng._bias_colsum(P, H.rows(dz), Mi, NF, c.mapb, g(c.b))
             h, w = h // 2, w // 2
@@ -279,7 +279,7 @@ class NearestConvTail(_Tail):
             H.act_grad_cast(G_lo, NF, src, NF, nxt, NF, Mo, NF, 2, 0.2 if i == 1 else 0.01)
             dz = nxt
         c = self.cbu
-        eng._nt(H.im2col(P["da0"], Hh, Ww, NF, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * NF, cd)
+        eng._nt(H.im2col(P["da0"], Hh, Ww, NF, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * NF)
         eng._wgrad(P, H.rows(P["da0"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=eng.C), M, NF, 9 * Cp, c.map,
                    g(c.w), g(c.b), eng.C)
 
@@ -298,13 +298,12 @@ class _OneConvTail(_Tail):
 
     def forward(self, eng, P):
         c, Cp, Hh, Ww = self.c, eng.Cp, P["H"], P["W"]
-        eng._nt(eng._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(), self._epilogue(eng, P, Hh, Ww), P["M"], c.Cop, 9 * Cp,
-                eng.cd)
+        eng._nt(eng._ain(H.im2col(P["fb"], Hh, Ww, Cp)), c.fwd(), self._epilogue(eng, P, Hh, Ww), P["M"], c.Cop, 9 * Cp)
         return P["E"]
 
     def backward(self, eng, P, grads):
         c, Cp, M, Hh, Ww = self.c, eng.Cp, P["M"], P["H"], P["W"]
-        eng._nt(H.im2col(P["dE"], Hh, Ww, c.Cop, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * c.Cop, eng.cd)
+        eng._nt(H.im2col(P["dE"], Hh, Ww, c.Cop, flip=True), H.rows(c.Wd), H.epilogue(P["dfb"]), M, Cp, 9 * c.Cop)
         eng._wgrad(P, H.rows(P["dE"]), H.im2col(P["fb"], Hh, Ww, Cp, ones_col=eng.C), M, c.Cop, 9 * Cp, c.map,
                    grads[c.w], grads[c.b], eng.C)
 

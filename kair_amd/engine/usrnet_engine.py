@@ -25,8 +25,6 @@ backward.  B*Hp*Wp < 2^24.
 import torch
 
 from .. import _hip as H
-from .base import lease_grads
-from .plans import Lease, autograd_mode, plan_mode
 from .resunet import C8, ResUNetProgram
 
 
@@ -159,8 +157,7 @@ class USRNetEngine(ResUNetProgram):
     def backward_from_grad(self, gE, grads):
         P = self.cur
         H.image_to_nhwc(gE.contiguous(), P["gE"], C8, None, 1.0, P["B"], self.out_nc, P["H"], P["W"])
-        if self.x3:   # an arbitrary upstream gradient: its exponent from its own range (one host sync)
-            P["e_g"] = self.x3_upstream_grad_exp(float(gE.abs().max()))
+        self._x3_set_grad_exp(P, gE)
         self.backward(grads, P)
 
     def backward(self, grads, P):
@@ -193,26 +190,3 @@ class USRNetEngine(ResUNetProgram):
         hp = self._hyp()
         H.hypanet_bwd(P["sig"], float(sf), *hp, self.hc, self.no, B, gab, *[grads[t] for t in hp])
 
-
-class USRNetFunction(torch.autograd.Function):
-    """The whole unfolded USRNet forward/backward as one autograd node (params are inputs); the
-    node leases its plan from forward to backward (kair_amd/engine/plans.py)."""
-
-    @classmethod
-    def run(cls, engine, x, k, sf, sigma, params):
-        return cls.apply(engine, autograd_mode(params), x, k, sf, sigma, *params)
-
-    @staticmethod
-    def forward(ctx, engine, mode, x, k, sf, sigma, *params):
-        with plan_mode(engine, mode):
-            E = engine.forward(x, k, sf, sigma)
-        ctx.engine, ctx.params = engine, params
-        ctx.lease = Lease(engine.cur) if mode == "lease" else None
-        return E.clone()
-
-    @staticmethod
-    def backward(ctx, gE):
-        _, grads = lease_grads(ctx, gE)
-        ctx.engine.backward_from_grad(gE.float(), grads)
-        ctx.lease.release()
-        return (None,) * 6 + tuple(grads[p] for p in ctx.params)

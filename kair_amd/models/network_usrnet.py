@@ -10,7 +10,8 @@ whole unfolded network as one autograd node on the HIP step program
 """
 import torch.nn as nn
 
-from ..engine.usrnet_engine import USRNetEngine, USRNetFunction
+from ..engine.base import ConvNetFunction
+from ..engine.usrnet_engine import USRNetEngine
 
 
 class ResBlock(nn.Module):
@@ -99,4 +100,4 @@ class USRNet(nn.Module):
     def forward(self, x, k, sf, sigma):
         if not x.is_cuda:
             raise RuntimeError("kair_amd USRNet runs on the MI355X (HIP) only; got a CPU tensor (no CPU fallback)")
-        return USRNetFunction.run(self.engine(), x, k, int(sf), sigma, list(self.parameters()))
+        return ConvNetFunction.run(self.engine(), x, list(self.parameters()), k, int(sf), sigma)

@@ -12,7 +12,9 @@ import pytest
 import torch.nn as nn
 
 from kair_amd.engine.base import ConvEngineBase, EngineBase
-from kair_amd.engine.dncnn_engine import DnCNNEngine
+from kair_amd.engine.dncnn_engine import DnCNNEngine, FFDNetEngine
+from kair_amd.engine.drunet_engine import DRUNetEngine
+from kair_amd.engine.resunet import ResUNetProgram
 from kair_amd.engine.rrdbnet_engine import RRDBNetEngine
 from kair_amd.engine.swinir_engine import SwinIREngine
 from kair_amd.engine.usrnet_engine import USRNetEngine
@@ -40,8 +42,11 @@ def test_inheritance_and_single_definitions():
     for cls in (RRDBNetEngine, DnCNNEngine, USRNetEngine):
         assert issubclass(cls, ConvEngineBase)
     assert not issubclass(SwinIREngine, ConvEngineBase)
-    for cls in ENGINES + (EngineBase, ConvEngineBase):
-        assert ("_nt" in vars(cls)) == (cls in (SwinIREngine, ConvEngineBase)), cls.__name__
+    for cls in ENGINES + (ConvEngineBase, ResUNetProgram, FFDNetEngine, DRUNetEngine):   # the launch layer: base.py only
+        for name in ("_nt", "_wgrad"):
+            assert name in vars(EngineBase) and name not in vars(cls), (cls.__name__, name)
+        assert ("conv_wgrad" in vars(cls)) == (cls is ConvEngineBase), cls.__name__
+    assert "conv_wgrad" not in vars(EngineBase)
     assert [cls.COMPUTE_DTYPES for cls in ENGINES] == [X3_ALL, X3_ALL, ("bf16", "fp32"), X3_ALL]
     assert (EngineBase.X3_AEXP, EngineBase.X3_BACKOFF_STEP, EngineBase.X3_BACKOFF_MAX) == (4, 6, 4)
 
@@ -108,7 +113,11 @@ def test_conv_engines_do_not_import_swinir_engine():
     assert r.returncode == 0, r.stdout + r.stderr[-2000:]
 
 
-@pytest.mark.parametrize("pattern", [r"def x3_backoff\b", r"def _x3_grad_exp\b", r"math\.ceil\(math\.log2"])
+FUNCTION_NODE = r"class \w+Function\(torch\.autograd\.Function\)"   # one for the conv programs, SwinIR's own
+
+
+@pytest.mark.parametrize("pattern", [r"def x3_backoff\b", r"def _x3_grad_exp\b", r"math\.ceil\(math\.log2", r"def _nt\b",
+                                     r"def _wgrad\b", FUNCTION_NODE])
 def test_defined_once_under_engine(pattern):
     d = os.path.join(ROOT, "kair_amd", "engine")
     hits = []
@@ -116,7 +125,7 @@ def test_defined_once_under_engine(pattern):
         if f.endswith(".py"):
             with open(os.path.join(d, f)) as fh:
                 hits += [f] * len(re.findall(pattern, fh.read()))
-    assert hits == ["base.py"], hits
+    assert hits == (["base.py", "swinir_engine.py"] if pattern == FUNCTION_NODE else ["base.py"]), hits
 
 
 def test_swinir_tail_and_conv_wr_rule_single_sourced():

@@ -1,12 +1,14 @@
-"""Bit-level record of the SwinIR step program, for refactors that must not change what it computes.
+"""Bit-level record of the step programs, for refactors that must not change what they compute.
 
     python tools/engine_digest.py [--only SUBSTRING] > digest.txt
 
-One line per case: the case name, SHA-256 of the output E, of the loss and of the flat gradient buffer, then
+One line per case: the case name, SHA-256 of the output E, of the loss and of the flat gradient buffer, then (SwinIR)
 P["conv_wr"] and (embed 180 cases) the kair_conv3x3_wr tiles of the tail shapes, which say what tail kernels ran.
 The step is deterministic (fixed weight-gradient partial planes, deterministic finalize), so two trees that issue
 the same launches on the same arguments print the same file; `diff` is the check.  Uses only SwinIR(...),
-SwinIREngine(net, dt, side_stream=..., ...), forward, backward_from_loss and backward_from_grad.
+SwinIREngine(net, dt, side_stream=..., ...), forward, backward_from_loss and backward_from_grad; the conv.* cases
+(RRDBNet, DnCNN, FFDNet, DRUNet, USRNet) the network constructors, net.engine() and the same three engine calls, the
+USRNet ones net(x, k, sf, sigma) and .backward() as well.
 """
 import argparse
 import hashlib
@@ -86,6 +88,81 @@ def run(name, kw, lr, dt, ekw, min_tiles, from_grad, dev):
     print(f"{name} E={hE} loss={sha(loss)} grad={sha(flat)} finite={bool(torch.isfinite(flat).all())} {extra}", flush=True)
 
 
+def _usr_kernel(g):
+    k = torch.rand(B, 1, 25, 25, generator=g)
+    return k / k.sum((-2, -1), keepdim=True)
+
+
+def conv_cases():
+    """(name, engine class, network factory(compute dtype), input shape, extra forward inputs(generator), modes): the
+    conv step programs at the small configurations of their tests, B = 2, run in every dtype the engine implements.
+    modes: "loss" (backward_from_loss), "grad" (backward_from_grad), "module" (the nn.Module and .backward(): the
+    autograd node)."""
+    from kair_amd.engine.dncnn_engine import DnCNNEngine, FFDNetEngine
+    from kair_amd.engine.drunet_engine import DRUNetEngine
+    from kair_amd.engine.rrdbnet_engine import RRDBNetEngine
+    from kair_amd.engine.usrnet_engine import USRNetEngine
+    from kair_amd.models.network_dncnn import DnCNN
+    from kair_amd.models.network_ffdnet import FFDNet
+    from kair_amd.models.network_rrdbnet import RRDBNet
+    from kair_amd.models.network_unet import UNetRes
+    from kair_amd.models.network_usrnet import USRNet
+    none = lambda g: ()
+    sigma = lambda g: ((torch.tensor([5.0, 50.0]) / 255).view(B, 1, 1, 1),)
+    usr = lambda sf: (lambda g: (_usr_kernel(g), sf, torch.rand(B, 1, 1, 1, generator=g) * (25.0 / 255)))
+    usrnet = lambda dt: USRNet(n_iter=2, h_nc=32, in_nc=4, out_nc=3, nc=[16, 32, 64, 64], nb=2, compute_dtype=dt)
+    both = ("loss", "grad")
+    for sf in (2, 4):
+        yield (f"rrdbnet_x{sf}", RRDBNetEngine, (lambda dt, sf=sf: RRDBNet(3, 3, 32, 1, 16, sf, compute_dtype=dt)),
+               (B, 3, 12, 12), none, both)
+    for tag, act in (("bn", "BR"), ("nobn", "R")):
+        yield (f"dncnn_{tag}", DnCNNEngine, (lambda dt, act=act: DnCNN(1, 1, 32, 5, act, compute_dtype=dt)),
+               (B, 1, 16, 20), none, both)
+    yield ("ffdnet_even", FFDNetEngine, (lambda dt: FFDNet(1, 1, 16, 4, "R", compute_dtype=dt)), (B, 1, 12, 20), sigma,
+           both)
+    # (an odd size has no fused loss: forward and backward_from_grad)
+    yield ("ffdnet_odd", FFDNetEngine, (lambda dt: FFDNet(3, 3, 16, 3, "R", compute_dtype=dt)), (B, 3, 9, 11), sigma,
+           ("grad",))
+    yield ("drunet", DRUNetEngine, (lambda dt: UNetRes(2, 1, (16, 32, 48, 64), 2, compute_dtype=dt)), (B, 2, 16, 24),
+           none, both)
+    # USRNet, 2 iterations: sf 2 on a 32 x 32 HR grid; sf 3 at 18 x 18 -> 54 x 54, which needs the replicate pad
+    yield "usrnet_sf2", USRNetEngine, usrnet, (B, 3, 16, 16), usr(2), both + ("module",)
+    yield "usrnet_pad", USRNetEngine, usrnet, (B, 3, 18, 18), usr(3), both + ("module",)
+
+
+def run_conv(name, make, shape, cond_of, mode, dt, dev):
+    torch.manual_seed(1234)
+    net = make(dt).to(dev).train()
+    g = torch.Generator().manual_seed(99)
+    x = torch.rand(*shape, generator=g).to(dev)
+    cond = tuple(c.to(dev) if torch.is_tensor(c) else c for c in cond_of(g))
+    params = list(net.parameters())
+    if mode == "module":
+        E = net(x, *cond)
+        hE = sha(E)
+        tgt = torch.rand(*E.shape, generator=g).to(dev)
+        E.backward((tgt - 0.5) / tgt.numel())
+        loss, flat = torch.zeros(1), torch.cat([p.grad.reshape(-1) for p in params])
+    else:
+        eng = net.engine()
+        flat = torch.zeros(sum(p.numel() for p in params), device=dev)
+        grads, off = {}, 0
+        for p in params:
+            grads[p] = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        E = eng.forward(x, *cond)
+        hE = sha(E)
+        tgt = torch.rand(*E.shape, generator=g).to(dev)
+        if mode == "grad":
+            eng.backward_from_grad((tgt - 0.5) / tgt.numel(), grads)
+            loss = torch.zeros(1)
+        else:
+            loss = eng.backward_from_loss(tgt, grads)
+    torch.cuda.synchronize()
+    print(f"conv.{name}.{dt}.{mode} E={hE} loss={sha(loss)} grad={sha(flat)} finite={bool(torch.isfinite(flat).all())}",
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="run the cases whose name contains this")
@@ -94,6 +171,11 @@ def main():
     for c in cases():
         if a.only in c[0]:
             run(*c, dev)
+    for name, engine_cls, make, shape, cond_of, modes in conv_cases():
+        for dt in engine_cls.COMPUTE_DTYPES:
+            for mode in modes:
+                if a.only in f"conv.{name}.{dt}.{mode}":
+                    run_conv(name, make, shape, cond_of, mode, dt, dev)
 
 
 if __name__ == "__main__":
