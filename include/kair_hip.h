@@ -113,6 +113,17 @@ typedef enum {
 
 typedef enum { KAIR_ACT_NONE = 0, KAIR_ACT_GELU = 1, KAIR_ACT_LEAKY = 2, KAIR_ACT_RELU = 3 } kair_act;
 
+/* The epilogue of kair_gemm_nt.  bias and act apply in every store mode.  Of the optional fields gate, resid,
+ * resid2, rowscale, the window map (win_ws > 0), out_pre and out_ones_col_p1 each mode reads only these; setting
+ * any other of them is KAIR_ERR_ARG (nothing is launched), as is a gate with a gate_kind outside 1..4:
+ *   KAIR_OUT_ROWS:        gate (kinds 1..4), resid, resid2, rowscale (with resid), window map, out_pre, out_ones_col_p1
+ *   KAIR_OUT_QKVBLK:      none
+ *   KAIR_OUT_PSHUF:       out_pre
+ *   KAIR_OUT_PUNSHUF:     gate (kinds 2..4; row and column of the unshuffled output)
+ *   KAIR_OUT_NCHW:        resid (an NCHW image of the output's shape, added after 1 / img_range and img_mean)
+ *   KAIR_OUT_PSHUF_NCHW:  none
+ *   KAIR_OUT_PSHUF_SPM:   out_pre
+ *   KAIR_OUT_PUNSHUF_SPM: gate (kinds 2..4; row and column of the unshuffled output) */
 typedef struct {
   void* out; int out_dtype; int out_mode; long ldo;
   int win_H, win_W, win_ws, win_shift;  /* row map for KAIR_OUT_ROWS / residual / gate         */

@@ -1654,6 +1654,27 @@ extern "C" int kair_gemm_nt(const kair_operand* A, const kair_operand* B, const 
   if ((rc = kair_check_operand(A, "gemm_nt A"))) return rc;
   if ((rc = kair_check_operand(B, "gemm_nt B"))) return rc;
   KAIR_CHECK_ARG(E && E->out, "gemm_nt: null epilogue/out");
+  {  // optional epilogue fields that the store mode does not read are argument errors, not silently dropped
+     // (the per-mode list of the kair_epilogue comment in kair_hip.h; no specialised kernel reads more)
+    const int om = E->out_mode;
+    const bool rows = om == KAIR_OUT_ROWS, punshuf = om == KAIR_OUT_PUNSHUF || om == KAIR_OUT_PUNSHUF_SPM;
+    KAIR_CHECK_ARG(!E->gate || rows || punshuf,
+                   "gemm_nt: gate is read only by the ROWS, PUNSHUF and PUNSHUF_SPM stores (out_mode %d)", om);
+    KAIR_CHECK_ARG(!E->gate || (E->gate_kind >= 1 && E->gate_kind <= 4), "gemm_nt: gate_kind %d is none of 1..4",
+                   E->gate_kind);
+    KAIR_CHECK_ARG(!E->gate || !punshuf || E->gate_kind != 1,
+                   "gemm_nt: gate_kind 1 (GELU') is not computed by the PUNSHUF / PUNSHUF_SPM stores");
+    KAIR_CHECK_ARG(!E->resid2 || rows, "gemm_nt: resid2 is read only by the ROWS store (out_mode %d)", om);
+    KAIR_CHECK_ARG(!E->rowscale || rows, "gemm_nt: rowscale is read only by the ROWS store (out_mode %d)", om);
+    KAIR_CHECK_ARG(E->win_ws == 0 || rows, "gemm_nt: the window map (win_ws) is read only by the ROWS store (out_mode %d)",
+                   om);
+    KAIR_CHECK_ARG(!E->resid || rows || om == KAIR_OUT_NCHW,
+                   "gemm_nt: resid is read only by the ROWS and NCHW stores (out_mode %d)", om);
+    KAIR_CHECK_ARG(!E->out_pre || rows || om == KAIR_OUT_PSHUF || om == KAIR_OUT_PSHUF_SPM,
+                   "gemm_nt: out_pre is written only by the ROWS, PSHUF and PSHUF_SPM stores (out_mode %d)", om);
+    KAIR_CHECK_ARG(E->out_ones_col_p1 <= 0 || rows,
+                   "gemm_nt: out_ones_col_p1 is read only by the ROWS store (out_mode %d)", om);
+  }
   if (compute == KAIR_COMPUTE_X3) return kair_gemm_nt_x3(A, B, E, M, N, K, stream);   // gemm_x3.hip
   KAIR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0, "gemm_nt: bad M/N/K (%ld,%d,%d), K%%8 must be 0", M, N, K);
   KAIR_CHECK_ARG(B->mode == KAIR_LD_ROWS && B->dtype == compute && B->win_ws == 0,
