@@ -992,20 +992,60 @@ def bn_bwd(z, ldz, a, lda, da, ldda, dz, lddz, M, C, gamma, mean, rstd, act, slo
 
 
 # ------------------------------------------------------------------------------------------
-# training-patch synthesis (kair_amd/data/gpu_synth.py)
+# training-patch synthesis (kair_amd/data/gpu_synth.py: one task class per wrapper family below)
 # ------------------------------------------------------------------------------------------
+def _rows_of(t, dtype, ncol, what):
+    """(pointer, row stride) of a [B, >= ncol] parameter table; a column slice of a wider table is fine."""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] < ncol or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: expected a [B, >= {ncol}] {dtype} table with unit column stride")
+    return ptr(t), t.stride(0)
+
+
+def _sample_rows(t, B, ncol, what, packed=False):
+    """_rows_of an int32 table that has a row for each of B samples.  packed: the kernel reads the rows as int4, so the
+    table is exactly [B, 4] with row stride 4 (no column slice of a wider table)."""
+    pp, ps = _rows_of(t, torch.int32, ncol, what)
+    if t.shape[0] < B:
+        raise ValueError(f"{what}: fewer parameter rows than samples")
+    if packed and (t.shape[1] != ncol or ps != ncol):
+        raise ValueError(f"{what}: expected packed [B, {ncol}] rows (row stride {ncol}), not a slice of a wider table")
+    return pp, ps
+
+
+def _fp32(t, shape, what):
+    """t is a contiguous fp32 tensor of exactly this shape."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be a contiguous fp32 {tuple(shape)}")
+
+
+def _images(t, what):
+    """(N, C, H, W) of a contiguous fp32 image batch (the pool, or whole images)."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4:
+        raise ValueError(f"{what} must be contiguous fp32 [N, C, H, W]")
+    return t.shape
+
+
 def synth_sr(pool, params, B, PS, sf, taps_h, taps_w, outH, outL):
+    """DatasetSR batch (kair_synth_sr): params [B, 4] int32 {image, rnd_h, rnd_w, mode}, packed; outH [B, C, PS, PS],
+    outL [B, C, PS // sf, PS // sf]."""
     require_device(pool, params, outH, outL)
-    N, C, Hs, Ws = pool.shape
+    N, C, Hs, Ws = _images(pool, "synth_sr: pool")
+    _fp32(outH, (B, C, PS, PS), "synth_sr: output")
+    _fp32(outL, (B, C, PS // sf, PS // sf), "synth_sr: output")
+    pp, _ = _sample_rows(params, B, 4, "synth_sr params", packed=True)
     (ih, wh), (iw, ww) = taps_h, taps_w
-    check(lib().kair_synth_sr(ptr(pool), C, Hs, Ws, ptr(params), B, PS, sf, ptr(wh), ptr(ih), ptr(ww), ptr(iw),
+    check(lib().kair_synth_sr(ptr(pool), C, Hs, Ws, pp, B, PS, sf, ptr(wh), ptr(ih), ptr(ww), ptr(iw),
                               wh.shape[1], ptr(outH), ptr(outL), stream_ptr()), "synth_sr")
 
 
 def synth_dn(pool, params, B, PS, sigma, seed, step, outH, outL):
+    """DatasetDnCNN batch (kair_synth_dn): params as synth_sr's; outH and outL [B, C, PS, PS]."""
     require_device(pool, params, outH, outL)
-    N, C, Hs, Ws = pool.shape
-    check(lib().kair_synth_dn(ptr(pool), C, Hs, Ws, ptr(params), B, PS, sigma, seed, step, ptr(outH), ptr(outL),
+    N, C, Hs, Ws = _images(pool, "synth_dn: pool")
+    _fp32(outH, (B, C, PS, PS), "synth_dn: output")
+    _fp32(outL, (B, C, PS, PS), "synth_dn: output")
+    pp, _ = _sample_rows(params, B, 4, "synth_dn params", packed=True)
+    check(lib().kair_synth_dn(ptr(pool), C, Hs, Ws, pp, B, PS, sigma, seed, step, ptr(outH), ptr(outL),
                               stream_ptr()), "synth_dn")
 
 
@@ -1013,15 +1053,10 @@ def synth_dn_map(pool, params, B, PS, seed, step, outH, outL, sigma_col=4):
     """FDnCNN / DRUNet batch (kair_synth_dn_map): params [B, >= 5] int32 {image, rnd_h, rnd_w, mode} plus the float32
     bits of the sample's sigma / 255 in column sigma_col; outH [B, C, PS, PS], outL [B, C + 1, PS, PS]."""
     require_device(pool, params, outH, outL)
-    N, C, Hs, Ws = pool.shape
-    if pool.dtype != torch.float32 or not pool.is_contiguous():
-        raise ValueError("synth_dn_map: pool must be contiguous fp32")
-    if params.shape[0] < B:
-        raise ValueError("synth_dn_map: fewer parameter rows than samples")
-    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C + 1, PS, PS))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise ValueError(f"synth_dn_map: output must be a contiguous fp32 {shp}")
-    pp, ps = _rows_of(params, torch.int32, max(5, sigma_col + 1), "synth_dn_map params")
+    N, C, Hs, Ws = _images(pool, "synth_dn_map: pool")
+    _fp32(outH, (B, C, PS, PS), "synth_dn_map: output")
+    _fp32(outL, (B, C + 1, PS, PS), "synth_dn_map: output")
+    pp, ps = _sample_rows(params, B, max(5, sigma_col + 1), "synth_dn_map params")
     check(lib().kair_synth_dn_map(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
                                   stream_ptr()), "synth_dn_map")
 
@@ -1030,26 +1065,14 @@ def synth_dn_level(pool, params, B, PS, seed, step, outH, outL, outC, sigma_col=
     """FFDNet batch (kair_synth_dn_level): synth_dn_map's parameter rows; outH and outL [B, C, PS, PS] (outL is
     synth_dn_map's outL[:, :C] bit for bit), the levels sigma / 255 in outC ([B] fp32, any shape of B elements)."""
     require_device(pool, params, outH, outL, outC)
-    N, C, Hs, Ws = pool.shape
-    if pool.dtype != torch.float32 or not pool.is_contiguous():
-        raise ValueError("synth_dn_level: pool must be contiguous fp32")
-    if params.shape[0] < B:
-        raise ValueError("synth_dn_level: fewer parameter rows than samples")
-    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C, PS, PS))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise ValueError(f"synth_dn_level: output must be a contiguous fp32 {shp}")
+    N, C, Hs, Ws = _images(pool, "synth_dn_level: pool")
+    _fp32(outH, (B, C, PS, PS), "synth_dn_level: output")
+    _fp32(outL, (B, C, PS, PS), "synth_dn_level: output")
     if outC.dtype != torch.float32 or not outC.is_contiguous() or outC.numel() != B:
         raise ValueError(f"synth_dn_level: outC must hold {B} contiguous fp32 levels")
-    pp, ps = _rows_of(params, torch.int32, max(5, sigma_col + 1), "synth_dn_level params")
+    pp, ps = _sample_rows(params, B, max(5, sigma_col + 1), "synth_dn_level params")
     check(lib().kair_synth_dn_level(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
                                     ptr(outC), stream_ptr()), "synth_dn_level")
-
-
-def _rows_of(t, dtype, ncol, what):
-    """(pointer, row stride) of a [B, >= ncol] parameter table; a column slice of a wider table is fine."""
-    if t.dtype != dtype or t.dim() != 2 or t.shape[1] < ncol or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what}: expected a [B, >= {ncol}] {dtype} table with unit column stride")
-    return ptr(t), t.stride(0)
 
 
 def usr_gauss_kernels(gpar, kpar, bank, out):
@@ -1084,18 +1107,13 @@ def synth_usr(pool, params, B, PS, sf, k, sigma, trunc8, seed, step, outH, outL,
     """USRNet batch (kair_synth_usr): params [B, >= 4] int32 {image, rnd_h, rnd_w, mode}, k [B, 1, kh, kw],
     sigma fp32 [B] or None (noise off)."""
     require_device(pool, params, k, sigma, outH, outL)
-    N, C, Hs, Ws = pool.shape
+    N, C, Hs, Ws = _images(pool, "synth_usr: pool")
     kh, kw = k.shape[-2:]
-    ls = PS // sf
-    if pool.dtype != torch.float32 or not pool.is_contiguous() or k.dtype != torch.float32 or not k.is_contiguous() \
-            or k.numel() != B * kh * kw:
-        raise ValueError("synth_usr: pool / k must be contiguous fp32, k [B, 1, kh, kw]")
-    if params.shape[0] < B:
-        raise ValueError("synth_usr: fewer parameter rows than samples")
-    for t, shp in ((outH, (B, C, PS, PS)), (outL, (B, C, ls, ls))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise ValueError(f"synth_usr: output must be a contiguous fp32 {shp}")
-    pp, ps = _rows_of(params, torch.int32, 4, "synth_usr params")
+    if k.dtype != torch.float32 or not k.is_contiguous() or k.numel() != B * kh * kw:
+        raise ValueError("synth_usr: k must be contiguous fp32 [B, 1, kh, kw]")
+    _fp32(outH, (B, C, PS, PS), "synth_usr: output")
+    _fp32(outL, (B, C, PS // sf, PS // sf), "synth_usr: output")
+    pp, ps = _sample_rows(params, B, 4, "synth_usr params")
     sp, ss = _usr_sigma(sigma, B, "synth_usr")
     check(lib().kair_synth_usr(ptr(pool), N, C, Hs, Ws, pp, ps, B, PS, sf, ptr(k), kh, kw, sp, ss, int(trunc8), seed, step,
                                ptr(outH), ptr(outL), int(direct), stream_ptr()), "synth_usr")
@@ -1104,14 +1122,11 @@ def synth_usr(pool, params, B, PS, sf, k, sigma, trunc8, seed, step, outH, outL,
 def usr_degrade(x, k, sf, sigma, trunc8, seed, step, outL, direct=False):
     """L of whole images x [N, C, Hs, Ws] (kair_usr_degrade): k [N, 1, kh, kw] or one [kh, kw] kernel for all."""
     require_device(x, k, sigma, outL)
-    N, C, Hs, Ws = x.shape
+    N, C, Hs, Ws = _images(x, "usr_degrade: x")
     kh, kw = k.shape[-2:]
-    if x.dtype != torch.float32 or not x.is_contiguous() or k.dtype != torch.float32 or not k.is_contiguous() \
-            or k.numel() not in (kh * kw, N * kh * kw):
-        raise ValueError("usr_degrade: x / k must be contiguous fp32, k [N, 1, kh, kw] or [kh, kw]")
-    shp = (N, C, -(-Hs // sf), -(-Ws // sf))
-    if outL.dtype != torch.float32 or not outL.is_contiguous() or tuple(outL.shape) != shp:
-        raise ValueError(f"usr_degrade: output must be a contiguous fp32 {shp}")
+    if k.dtype != torch.float32 or not k.is_contiguous() or k.numel() not in (kh * kw, N * kh * kw):
+        raise ValueError("usr_degrade: k must be contiguous fp32 [N, 1, kh, kw] or [kh, kw]")
+    _fp32(outL, (N, C, -(-Hs // sf), -(-Ws // sf)), "usr_degrade: output")
     sp, ss = _usr_sigma(sigma, N, "usr_degrade")
     kstride = 0 if k.numel() == kh * kw else kh * kw
     check(lib().kair_usr_degrade(ptr(x), N, C, Hs, Ws, sf, ptr(k), kstride, kh, kw, sp, ss, int(trunc8), seed, step,
@@ -1122,10 +1137,8 @@ def jpeg_roundtrip(x, quality, out):
     """out <- the JPEG round trip of x [N, 1 or 3, H, W] fp32 in [0, 1] (kair_jpeg_roundtrip); quality: device int32,
     one entry for all samples or N entries.  Returns the error code of a refused call through RuntimeError."""
     require_device(x, quality, out)
-    N, C, Hh, W = x.shape
-    if x.dtype != torch.float32 or not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.shape != x.shape:
-        raise ValueError("jpeg_roundtrip: x / out must be contiguous fp32 of one shape")
+    N, C, Hh, W = _images(x, "jpeg_roundtrip: x")
+    _fp32(out, x.shape, "jpeg_roundtrip: out")
     if quality.dtype != torch.int32 or quality.dim() != 1 or quality.shape[0] not in (1, N):
         raise ValueError("jpeg_roundtrip: quality must be an int32 vector of 1 or N entries")
     qstride = 0 if quality.shape[0] == 1 else quality.stride(0)
@@ -1142,10 +1155,9 @@ def jpeg_roundtrip(x, quality, out):
 def rgb2gray8(x, mode, out):
     """out [N, 1, H, W] <- gray uint8 / 255 of x [N, 3, H, W] (kair_rgb2gray8): mode 0 rgb2ycbcr Y, mode 1 OpenCV."""
     require_device(x, out)
-    N, C, Hh, W = x.shape
-    if C != 3 or x.dtype != torch.float32 or not x.is_contiguous() or out.dtype != torch.float32 \
-            or not out.is_contiguous() or tuple(out.shape) != (N, 1, Hh, W):
-        raise ValueError("rgb2gray8: x must be a contiguous fp32 [N, 3, H, W], out [N, 1, H, W]")
+    N, _, Hh, W = x.shape
+    _fp32(x, (N, 3, Hh, W), "rgb2gray8: x")
+    _fp32(out, (N, 1, Hh, W), "rgb2gray8: out")
     check(lib().kair_rgb2gray8(ptr(x), N, Hh, W, int(mode), ptr(out), stream_ptr()), "rgb2gray8")
 
 
@@ -1153,16 +1165,10 @@ def synth_jpeg(pool, params, B, PS, is_color, outH, outL):
     """JPEG CAR batch (kair_synth_jpeg): params [B, >= 8] int32 {image, rnd_h, rnd_w, mode, gray_mode, quality, rh2,
     rw2}; outH / outL [B, 3 if is_color else 1, PS, PS]."""
     require_device(pool, params, outH, outL)
-    N, C, Hs, Ws = pool.shape
-    if pool.dtype != torch.float32 or not pool.is_contiguous():
-        raise ValueError("synth_jpeg: pool must be contiguous fp32")
-    if params.shape[0] < B:
-        raise ValueError("synth_jpeg: fewer parameter rows than samples")
-    shp = (B, 3 if is_color else 1, PS, PS)
+    N, C, Hs, Ws = _images(pool, "synth_jpeg: pool")
     for t in (outH, outL):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise ValueError(f"synth_jpeg: output must be a contiguous fp32 {shp}")
-    pp, ps = _rows_of(params, torch.int32, 8, "synth_jpeg params")
+        _fp32(t, (B, 3 if is_color else 1, PS, PS), "synth_jpeg: output")
+    pp, ps = _sample_rows(params, B, 8, "synth_jpeg params")
     check(lib().kair_synth_jpeg(ptr(pool), N, C, Hs, Ws, pp, ps, B, PS, int(bool(is_color)), ptr(outH), ptr(outL),
                                 stream_ptr()), "synth_jpeg")
 
@@ -1177,12 +1183,9 @@ def bsr_crop(pool, head, B, PS, dst):
     """dst [B, 3, PS, PS] <- the augmented crops of head [B, >= 6] int32 {image, rnd_h, rnd_w, mode, lq_h, lq_w}
     (kair_bsr_crop)."""
     require_device(pool, head, dst)
-    N, C, Hs, Ws = pool.shape
-    if pool.dtype != torch.float32 or not pool.is_contiguous() or _bsr_buf(dst, "bsr_crop") != (B, PS, PS):
-        raise ValueError("bsr_crop: pool must be contiguous fp32, dst [B, 3, PS, PS]")
-    if head.shape[0] < B:
-        raise ValueError("bsr_crop: fewer parameter rows than samples")
-    hp, hs = _rows_of(head, torch.int32, 6, "bsr_crop head")
+    N, C, Hs, Ws = _images(pool, "bsr_crop: pool")
+    _fp32(dst, (B, 3, PS, PS), "bsr_crop: dst")
+    hp, hs = _sample_rows(head, B, 6, "bsr_crop head")
     check(lib().kair_bsr_crop(ptr(pool), N, C, Hs, Ws, hp, hs, B, PS, ptr(dst), stream_ptr()), "bsr_crop")
 
 
@@ -1190,15 +1193,11 @@ def bsr_finish(pool, head, B, PS, sf, lq, src, outL, outH):
     """outL [B, 3, lq, lq] <- the crop of the buffer src [B, 3, PS, PS] at head's (lq_h, lq_w); outH [B, 3, lq sf, lq sf]
     <- the aligned crop of the augmented pool patch (kair_bsr_finish)."""
     require_device(pool, head, src, outL, outH)
-    N, C, Hs, Ws = pool.shape
-    if pool.dtype != torch.float32 or not pool.is_contiguous() or _bsr_buf(src, "bsr_finish") != (B, PS, PS):
-        raise ValueError("bsr_finish: pool must be contiguous fp32, src [B, 3, PS, PS]")
-    for t, shp in ((outL, (B, 3, lq, lq)), (outH, (B, 3, lq * sf, lq * sf))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise ValueError(f"bsr_finish: output must be a contiguous fp32 {shp}")
-    if head.shape[0] < B:
-        raise ValueError("bsr_finish: fewer parameter rows than samples")
-    hp, hs = _rows_of(head, torch.int32, 6, "bsr_finish head")
+    N, C, Hs, Ws = _images(pool, "bsr_finish: pool")
+    _fp32(src, (B, 3, PS, PS), "bsr_finish: src")
+    _fp32(outL, (B, 3, lq, lq), "bsr_finish: output")
+    _fp32(outH, (B, 3, lq * sf, lq * sf), "bsr_finish: output")
+    hp, hs = _sample_rows(head, B, 6, "bsr_finish head")
     check(lib().kair_bsr_finish(ptr(pool), N, C, Hs, Ws, hp, hs, B, PS, sf, lq, ptr(src), ptr(outL), ptr(outH),
                                 stream_ptr()), "bsr_finish")
 

@@ -55,9 +55,13 @@ class DatasetFDnCNN(data.Dataset):
             img_L += np.random.normal(0, self.sigma_test / 255.0, img_L.shape)
             noise_level = torch.FloatTensor([self.sigma_test / 255.0])
             img_L, img_H = util.single2tensor3(img_L), util.single2tensor3(img_H)
+        return {**self._with_level(img_L, img_H, noise_level), "L_path": H_path, "H_path": H_path}
+
+    def _with_level(self, img_L, img_H, noise_level):
+        """The last step of __getitem__, where the level joins the pair: here as the map channel of L (DatasetFFDNet
+        returns it as "C")."""
         noise_map = noise_level.view(1, 1, 1).repeat(1, img_L.size(1), img_L.size(2))
-        img_L = torch.cat((img_L, noise_map), 0)
-        return {"L": img_L, "H": img_H, "L_path": H_path, "H_path": H_path}
+        return {"L": torch.cat((img_L, noise_map), 0), "H": img_H}
 
     def __len__(self):
         return len(self.paths_H)

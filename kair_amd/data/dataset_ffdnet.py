@@ -10,34 +10,9 @@ The level is not concatenated into L: both branches return it as "C" of shape [1
 
 The GPU-resident equivalent is kair_amd.data.gpu_synth.PatchSynth(task="ffdnet") (kair_synth_dn_level, one launch).
 """
-import random
-
-import numpy as np
-import torch
-
-from ..utils import utils_image as util
 from .dataset_fdncnn import DatasetFDnCNN
 
 
 class DatasetFFDNet(DatasetFDnCNN):
-    def __getitem__(self, index):
-        H_path = self.paths_H[index]
-        img_H = util.imread_uint(H_path, self.n_channels)
-        if self.opt["phase"] == "train":
-            H, W, _ = img_H.shape
-            rnd_h = random.randint(0, max(0, H - self.patch_size))
-            rnd_w = random.randint(0, max(0, W - self.patch_size))
-            patch = img_H[rnd_h:rnd_h + self.patch_size, rnd_w:rnd_w + self.patch_size, :]
-            patch = util.augment_img(patch, mode=np.random.randint(0, 8))
-            img_H = util.uint2tensor3(patch)
-            img_L = img_H.clone()
-            noise_level = torch.FloatTensor([np.random.uniform(self.sigma_min, self.sigma_max)]) / 255.0
-            img_L.add_(torch.randn(img_L.size()).mul_(noise_level))
-        else:
-            img_H = util.uint2single(img_H)
-            img_L = np.copy(img_H)
-            np.random.seed(seed=0)
-            img_L += np.random.normal(0, self.sigma_test / 255.0, img_L.shape)
-            noise_level = torch.FloatTensor([self.sigma_test / 255.0])
-            img_L, img_H = util.single2tensor3(img_L), util.single2tensor3(img_H)
-        return {"L": img_L, "H": img_H, "C": noise_level.view(1, 1, 1), "L_path": H_path, "H_path": H_path}
+    def _with_level(self, img_L, img_H, noise_level):
+        return {"L": img_L, "H": img_H, "C": noise_level.view(1, 1, 1)}
