@@ -566,6 +566,14 @@ int kair_l1_loss(const float* E, const float* H, float* loss_out, void* dE, int 
  * kair_l1_loss. */
 int kair_charbonnier_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r,
                           float weight, float eps, int B, int C, int Hh, int Ww, float* ws, void* stream);
+/* L2 loss (G_lossfn_type 'l2' / 'l2sum'; model_plain.py:187-190 nn.MSELoss() / nn.MSELoss(reduction='sum')):
+ * sum_reduction == 0: loss_out[0] = weight*mean((E-H)^2), dE = 2*weight*(E-H)/numel; sum_reduction != 0: the same
+ * without the division by numel in both.  The gradient is one fp32 product of E-H and the rounded constant.  dE laid
+ * out as kair_l1_loss (dtype KAIR_F32 / KAIR_BF16, pad slots zero), ws: the same 1024 floats, summed in a fixed
+ * order: repeated calls are bit-identical.  Argument errors (null pointer, C*ps_r^2 > ldc, Hh or Ww not divisible by
+ * ps_r) launch nothing. */
+int kair_l2_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r, float weight,
+                 int sum_reduction, int B, int C, int Hh, int Ww, float* ws, void* stream);
 /* SSIM as a loss (G_lossfn_type 'ssim'; the reference's models/loss_ssim.py restated in kair_amd/models/model_plain.py
  * SSIMLoss): 11x11 Gaussian window (sigma 1.5, sum 1), depthwise, zero padding 5, C1 = 0.01^2, C2 = 0.03^2 (data
  * range 1), loss_out[0] = weight * mean over B, C, H, W of the SSIM map -- the SSIM itself, not 1 - SSIM: a run that
@@ -618,6 +626,24 @@ int kair_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long
 int kair_adam_ema_ex(float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t,
                      float beta1, float beta2, float eps, float weight_decay, float ema_decay, const unsigned* skip,
                      void* stream);
+/* Global gradient-norm clipping inside the step (G_optimizer_clipgrad; model_plain.py:296-298
+ * torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2)), device side: no host read of the norm.
+ * kair_grad_norm: norm_out[0] = sqrt(sum g_i^2) over n fp32 values.  Two launches on a fixed geometry: *grid
+ * workgroups of *block threads (kair_grad_norm_ws fills them when non-NULL and returns the workspace size in floats,
+ * one partial per workgroup); a thread sums the squares of its float4s (grid stride; g 16-byte aligned, else element
+ * by element) and of at most one tail element in fp32, a tree over the workgroup gives ws[workgroup], and one
+ * workgroup sums the partials in a fixed order in double.  No atomics: repeated calls are bit-identical.  The
+ * longest fp32 addition chain is 2 + ceil(floor(n/4) / (grid*block)) + 1 + log2(block). */
+long kair_grad_norm_ws(int* grid, int* block);
+int kair_grad_norm(const float* g, long n, float* ws, float* norm_out, void* stream);
+/* kair_adam_ema_ex on the clipped gradient g_i * coef, coef = min(1, max_norm / (gnorm[0] + 1e-6f)) in fp32
+ * (clip_grad_norm_'s arithmetic; gnorm: kair_grad_norm's device result).  coef < 1: the clipped gradient, rounded to
+ * fp32, is also stored back to g (what clip_grad_norm_ leaves in .grad); coef >= 1: bit-identical to
+ * kair_adam_ema_ex and g is not written (the branch is uniform over the grid).  *skip != 0: returns before touching
+ * anything, g included.  max_norm <= 0 or a NULL gnorm is an argument error. */
+int kair_adam_ema_clip(float* p, float* g, float* m, float* v, float* ema, long n, const float* lr_t, float beta1,
+                       float beta2, float eps, float weight_decay, float ema_decay, const unsigned* skip,
+                       const float* gnorm, float max_norm, void* stream);
 /* fp32x3 range guard: *flag = (any non-finite g: 1) | (non-finite *loss: 2) | (any |p| >= p_limit or
  * non-finite p: 4), over the flat gradient / parameter buffers of n floats (loss may be NULL).  A split-fp16
  * operand that leaves fp16's range turns into inf/NaN in every product it enters, so the step's gradients

@@ -196,6 +196,11 @@ _SIGS = {
     "kair_adam_ema": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_float, c_float, c_float, c_float, c_float, c_vp],
     "kair_adam_ema_ex": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_float, c_float, c_float, c_float, c_float, c_vp,
                          c_vp],
+    "kair_l2_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_grad_norm_ws": [ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
+    "kair_grad_norm": [c_vp, c_long, c_vp, c_vp, c_vp],
+    "kair_adam_ema_clip": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_float, c_float, c_float, c_float, c_float, c_vp,
+                           c_vp, c_float, c_vp],
     "kair_range_check": [c_vp, c_vp, c_long, c_vp, c_float, c_vp, c_vp],
     "kair_gate_hold": [c_int, c_vp],
     "kair_gate_release": [],
@@ -265,7 +270,8 @@ _SIGS = {
 _RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": c_long, "kair_rowgemm_ln_blocks": c_long, "kair_window_attn_bwd_groups": c_long, "kair_wgrad_grouped_ws": c_long, "kair_swin_mlp_bwd_ws": c_long, "kair_bn_ws": c_long, "kair_colsum_ws": c_long, "kair_last_error": ctypes.c_char_p, "kair_window_attn_bwd_ws": c_long, "kair_window_attn_bwd_ws_w": c_long, "kair_pack_table_bytes": c_long,
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
-            "kair_jpeg_workspace_bytes": c_long, "kair_ssim_workspace_bytes": c_long}
+            "kair_jpeg_workspace_bytes": c_long, "kair_ssim_workspace_bytes": c_long,
+            "kair_grad_norm_ws": c_long}
 
 _lib = None
 
@@ -891,6 +897,44 @@ def ktime_read(i):
     ms, name = ctypes.c_float(), ctypes.c_char_p()
     check(lib().kair_ktime_read(i, ctypes.byref(ms), ctypes.byref(name)), "ktime_read")
     return ms.value, (name.value or b"").decode(errors="replace")
+
+
+def l2_loss(E, H, loss_out, dE, ldc, weight, B, C, Hh, Ww, ws, ps_r=1, reduction="mean"):
+    """kair_l2_loss: weight * mean (reduction 'mean', nn.MSELoss()) or sum ('sum') of (E - H)^2 into loss_out, its
+    gradient into the dE rows (l1_loss's layouts).  ws: 1024 floats."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"l2_loss: reduction {reduction!r} ('mean' or 'sum')")
+    check(lib().kair_l2_loss(ptr(E), ptr(H), ptr(loss_out), ptr(dE), dtype_code(dE), ldc, ps_r, weight,
+                             int(reduction == "sum"), B, C, Hh, Ww, ptr(ws), stream_ptr()), "l2_loss")
+
+
+_GRAD_NORM_GEOM = None
+
+
+def grad_norm_geometry():
+    """(grid, block, workspace floats) of kair_grad_norm's first launch (kair_grad_norm_ws): fixed, whatever n is."""
+    global _GRAD_NORM_GEOM
+    if _GRAD_NORM_GEOM is None:
+        g, b = c_int(0), c_int(0)
+        n = lib().kair_grad_norm_ws(ctypes.byref(g), ctypes.byref(b))
+        _GRAD_NORM_GEOM = (g.value, b.value, n)
+    return _GRAD_NORM_GEOM
+
+
+def grad_norm(g, ws, norm_out):
+    """norm_out[0] = the 2-norm of the flat fp32 buffer g (kair_grad_norm); ws: grad_norm_geometry()[2] floats."""
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("grad_norm: g must be a contiguous fp32 tensor")
+    if ws.numel() < grad_norm_geometry()[2]:
+        raise ValueError(f"grad_norm: workspace too small ({ws.numel()} < {grad_norm_geometry()[2]} floats)")
+    check(lib().kair_grad_norm(ptr(g), g.numel(), ptr(ws), ptr(norm_out), stream_ptr()), "grad_norm")
+
+
+def adam_ema_clip(p, g, m, v, ema, n, lr_t, beta1, beta2, eps, wd, decay, gnorm, max_norm, skip=None):
+    """adam_ema on g * min(1, max_norm / (gnorm[0] + 1e-6)) (kair_adam_ema_clip); a step that clips also leaves the
+    clipped gradient in g.  gnorm: grad_norm's device result; skip as in adam_ema."""
+    check(lib().kair_adam_ema_clip(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(lr_t), beta1, beta2, eps, wd, decay,
+                                   ptr(skip), ptr(gnorm), float(max_norm), stream_ptr()), "adam_ema_clip")
 
 
 def range_check(g, p, loss, p_limit, flag):

@@ -681,8 +681,12 @@ __global__ __launch_bounds__(256) void ffd_pack_kernel(const float* __restrict__
 }
 
 // I: index type (int when every index fits: 32-bit divisions are a fraction of the 64-bit ones)
-// CH: Charbonnier (models/loss.py:208-218) sqrt(d^2 + eps) with gradient d / sqrt(d^2 + eps), else L1
-template <typename T, typename I, bool CH>
+// MODE: LOSS_L1 |d| with gradient sign(d); LOSS_CHARB: Charbonnier (models/loss.py:208-218) sqrt(d^2 + eps) with
+// gradient d / sqrt(d^2 + eps); LOSS_L2 (nn.MSELoss, model_plain.py:187-190): d^2 with gradient 2 d -- the 2 is in
+// gscale, so the gradient is one product of two rounded values
+enum { LOSS_L1 = 0, LOSS_CHARB = 1, LOSS_L2 = 2 };
+
+template <typename T, typename I, int MODE>
 __global__ void l1_kernel(const float* __restrict__ E, const float* __restrict__ H, T* __restrict__ dE, int ldc, int r,
                           float gscale, int C, int Hh, int Ww, long npix, float* __restrict__ ws, float eps) {
   // dE element t = (pixel of the [Hh/r, Ww/r] grid, channel slot); slot -> (c, i, j) when r > 1
@@ -702,10 +706,13 @@ __global__ void l1_kernel(const float* __restrict__ E, const float* __restrict__
       const int y = (pp / wsm) * r + ij / r, x = (pp % wsm) * r + ij % r;
       const I i = (b * C + c) * HW + (I)y * Ww + x;
       const float d = E[i] - H[i];
-      if constexpr (CH) {
+      if constexpr (MODE == LOSS_CHARB) {
         const float q = sqrtf(d * d + eps);
         s += q;
         g = q > 0.f ? gscale * d / q : 0.f;
+      } else if constexpr (MODE == LOSS_L2) {
+        s += d * d;
+        g = gscale * d;
       } else {
         s += fabsf(d);
         g = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
@@ -725,7 +732,7 @@ __global__ void l1_kernel(const float* __restrict__ E, const float* __restrict__
 // the same loss and gradient for the usual layout (r = 1, 16 bf16 slots per pixel, C <= 4): one thread per
 // pixel -- its C channel reads coalesced across the wave (NCHW planes), its 16 slots stored as two 16-byte
 // pieces -- instead of one thread per slot (16 threads per pixel, plane-strided reads, 2-byte stores)
-template <bool CH>
+template <int MODE>
 __global__ void l1_pix16_kernel(const float* __restrict__ E, const float* __restrict__ H, bf16* __restrict__ dE,
                                 float gscale, int C, int HW, int npix, float* __restrict__ ws, float eps) {
   __shared__ float red[256];
@@ -739,10 +746,13 @@ __global__ void l1_pix16_kernel(const float* __restrict__ E, const float* __rest
       const long i = ((long)b * C + c) * HW + pp;
       const float d = E[i] - H[i];
       float g;
-      if constexpr (CH) {
+      if constexpr (MODE == LOSS_CHARB) {
         const float q = sqrtf(d * d + eps);
         s += q;
         g = q > 0.f ? gscale * d / q : 0.f;
+      } else if constexpr (MODE == LOSS_L2) {
+        s += d * d;
+        g = gscale * d;
       } else {
         s += fabsf(d);
         g = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
@@ -764,7 +774,7 @@ __global__ void l1_pix16_kernel(const float* __restrict__ E, const float* __rest
 
 // fp32 gradient rows of 4 slots per pixel (C <= 4; the fp32x3 engine's conv_last narrow kernels read 4 channels):
 // one thread per pixel, one 16-byte store
-template <bool CH>
+template <int MODE>
 __global__ void l1_pix4f_kernel(const float* __restrict__ E, const float* __restrict__ H, float* __restrict__ dE,
                                 float gscale, int C, int HW, int npix, float* __restrict__ ws, float eps) {
   __shared__ float red[256];
@@ -777,10 +787,13 @@ __global__ void l1_pix4f_kernel(const float* __restrict__ E, const float* __rest
       if (c >= C) break;
       const long i = ((long)b * C + c) * HW + pp;
       const float d = E[i] - H[i];
-      if constexpr (CH) {
+      if constexpr (MODE == LOSS_CHARB) {
         const float q = sqrtf(d * d + eps);
         s += q;
         g4[c] = q > 0.f ? gscale * d / q : 0.f;
+      } else if constexpr (MODE == LOSS_L2) {
+        s += d * d;
+        g4[c] = gscale * d;
       } else {
         s += fabsf(d);
         g4[c] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
@@ -863,6 +876,87 @@ __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__
     p[i] = pi;
     if (ema) ema[i] = ema[i] * decay + (1.f - decay) * pi;
   }
+}
+
+// adam_ema_kernel's loop for kair_adam_ema_clip (the kernel above stays as it is: the unclipped step's launch is not
+// touched).  CLIP: the gradient is g * coef, rounded to fp32 and stored back to g before Adam reads it (what
+// torch.nn.utils.clip_grad_norm_ leaves in .grad: opaque() keeps the product out of the FMAs after it); else the
+// arithmetic of adam_ema_kernel, statement for statement
+template <bool CLIP>
+KAIR_DEV void adam_ema_clip_body(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, float* __restrict__ ema, long n, const float* __restrict__ lr_t,
+                                 float b1, float b2, float eps, float wd, float decay, float coef) {
+  const float step = lr_t[0], bc2s = lr_t[1];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float gi = g[i];
+    if constexpr (CLIP) {
+      gi = opaque(gi * coef);
+      g[i] = gi;
+    }
+    float pi = p[i];
+    if (wd != 0.f) gi = gi + wd * pi;
+    float mi = m[i];
+    mi = mi + (1.f - b1) * (gi - mi);
+    float vi = v[i] * b2;
+    vi = vi + (1.f - b2) * (gi * gi);
+    const float denom = sqrtf(vi) / bc2s + eps;
+    pi = pi + (-step) * (mi / denom);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+    if (ema) ema[i] = ema[i] * decay + (1.f - decay) * pi;
+  }
+}
+
+// kair_adam_ema_clip: coef = min(1, max_norm / (gnorm + 1e-6)) (clip_grad_norm_'s fp32 arithmetic), the same on every
+// thread: a step that does not clip (coef >= 1, or a NaN norm) runs the unclipped body and stores nothing to g
+__global__ void adam_ema_clip_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                     float* __restrict__ v, float* __restrict__ ema, long n,
+                                     const float* __restrict__ lr_t, float b1, float b2, float eps, float wd, float decay,
+                                     const unsigned* __restrict__ skip, const float* __restrict__ gnorm, float max_norm) {
+  if (skip && *skip) return;
+  const float coef = max_norm / (gnorm[0] + 1e-6f);
+  if (coef < 1.f) adam_ema_clip_body<true>(p, g, m, v, ema, n, lr_t, b1, b2, eps, wd, decay, coef);
+  else adam_ema_clip_body<false>(p, g, m, v, ema, n, lr_t, b1, b2, eps, wd, decay, 1.f);
+}
+
+// kair_grad_norm, stage 1 of 2: a fixed grid of GN_GRID x GN_BLOCK threads, each the fp32 sum of squares of its
+// float4s (grid stride) and of at most one tail element, then a tree over the workgroup -> ws[blockIdx.x].  The
+// longest fp32 addition chain is 2 (inside a float4) + float4s per thread + 1 (tail) + log2(GN_BLOCK) (tree).
+constexpr int GN_GRID = 1024, GN_BLOCK = 256;
+
+__global__ __launch_bounds__(GN_BLOCK) void grad_norm_partial_kernel(const float* __restrict__ g, long n,
+                                                                     float* __restrict__ ws) {
+  __shared__ float red[GN_BLOCK];
+  float s = 0.f;
+  const long n4 = ((uintptr_t)g & 15) == 0 ? n / 4 : 0;   // (a misaligned buffer: every element through the tail loop)
+  const long tid = (long)blockIdx.x * GN_BLOCK + threadIdx.x, nt = (long)GN_GRID * GN_BLOCK;
+  for (long i = tid; i < n4; i += nt) {
+    const float4 a = ((const float4*)g)[i];
+    s += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+  }
+  for (long i = n4 * 4 + tid; i < n; i += nt) s += g[i] * g[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = GN_BLOCK / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ws[blockIdx.x] = red[0];
+}
+
+// stage 2: one workgroup sums the GN_GRID partials in a fixed order, in double
+__global__ __launch_bounds__(GN_BLOCK) void grad_norm_final_kernel(const float* __restrict__ ws, float* __restrict__ out) {
+  __shared__ double red[GN_BLOCK];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < GN_GRID; i += GN_BLOCK) s += (double)ws[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = GN_BLOCK / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)sqrt(red[0]);
 }
 
 __global__ void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, float a, long n) {
@@ -1186,59 +1280,77 @@ extern "C" int kair_ffd_pack(const float* img, const float* sigma, void* out, in
   return 0;
 }
 
-static int pixel_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r, float weight,
-                      float eps, bool charb, int B, int C, int Hh, int Ww, float* ws, void* stream) {
-  KAIR_CHECK_ARG(E && H && loss_out && dE && ws && ps_r >= 1 && ldc >= C * ps_r * ps_r, "pixel loss: bad args");
-  KAIR_CHECK_ARG(Hh % ps_r == 0 && Ww % ps_r == 0, "pixel loss: image not divisible by r");
+// name: the entry point, for its argument errors.  mode: LOSS_*; sum_reduction (LOSS_L2 only): no division by numel
+static int pixel_loss(const char* name, const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc,
+                      int ps_r, float weight, float eps, int mode, bool sum_reduction, int B, int C, int Hh, int Ww,
+                      float* ws, void* stream) {
+  KAIR_CHECK_ARG(E && H && loss_out && dE && ws && ps_r >= 1 && ldc >= C * ps_r * ps_r, "%s: bad args", name);
+  KAIR_CHECK_ARG(Hh % ps_r == 0 && Ww % ps_r == 0, "%s: image not divisible by r", name);
   const long npix = (long)B * (Hh / ps_r) * (Ww / ps_r);
   const double numel = (double)B * Hh * Ww * C;
   const int nb = 1024;
   hipStream_t s = (hipStream_t)stream;
-  const float gs = (float)(weight / numel);
+  const double wn = sum_reduction ? (double)weight : weight / numel;
+  const float gs = (float)(mode == LOSS_L2 ? 2.0 * wn : wn);
   // int indices when the largest index (dE element or image element) and the grid stride fit
   const bool i32 = (double)npix * ldc < 2.0e9 && numel < 2.0e9;
   const bool pix4f = ps_r == 1 && ldc == 4 && C <= 4 && dtype == KAIR_F32 && npix < (1L << 31) && ((uintptr_t)dE & 15) == 0;
   if (pix4f || (ps_r == 1 && ldc == 16 && C <= 4 && dtype == KAIR_BF16 && npix < (1L << 31) && ((uintptr_t)dE & 15) == 0)) {
-    if (pix4f && charb) KAIR_LAUNCH(l1_pix4f_kernel<true>, dim3(nb), dim3(256), 0, s, E, H, (float*)dE, gs, C, Hh * Ww, (int)npix, ws, eps);
-    else if (pix4f) KAIR_LAUNCH(l1_pix4f_kernel<false>, dim3(nb), dim3(256), 0, s, E, H, (float*)dE, gs, C, Hh * Ww, (int)npix, ws, eps);
-    else if (charb) KAIR_LAUNCH(l1_pix16_kernel<true>, dim3(nb), dim3(256), 0, s, E, H, (bf16*)dE, gs, C, Hh * Ww, (int)npix, ws, eps);
-    else KAIR_LAUNCH(l1_pix16_kernel<false>, dim3(nb), dim3(256), 0, s, E, H, (bf16*)dE, gs, C, Hh * Ww, (int)npix, ws, eps);
+#define KAIR_PIX4F(M) KAIR_LAUNCH(l1_pix4f_kernel<M>, dim3(nb), dim3(256), 0, s, E, H, (float*)dE, gs, C, Hh * Ww, (int)npix, ws, eps)
+#define KAIR_PIX16(M) KAIR_LAUNCH(l1_pix16_kernel<M>, dim3(nb), dim3(256), 0, s, E, H, (bf16*)dE, gs, C, Hh * Ww, (int)npix, ws, eps)
+    if (pix4f && mode == LOSS_CHARB) KAIR_PIX4F(LOSS_CHARB);
+    else if (pix4f && mode == LOSS_L2) KAIR_PIX4F(LOSS_L2);
+    else if (pix4f) KAIR_PIX4F(LOSS_L1);
+    else if (mode == LOSS_CHARB) KAIR_PIX16(LOSS_CHARB);
+    else if (mode == LOSS_L2) KAIR_PIX16(LOSS_L2);
+    else KAIR_PIX16(LOSS_L1);
+#undef KAIR_PIX4F
+#undef KAIR_PIX16
     KAIR_CHECK_LAUNCH();
-    KAIR_LAUNCH(l1_final, dim3(1), dim3(256), 0, s, ws, nb, (float)(weight / numel), loss_out);
+    KAIR_LAUNCH(l1_final, dim3(1), dim3(256), 0, s, ws, nb, (float)wn, loss_out);
     KAIR_CHECK_LAUNCH();
     return 0;
   }
-#define KAIR_PIXEL_LOSS(T, I, CHV)                                                                                       \
-  KAIR_LAUNCH((l1_kernel<T, I, CHV>), dim3(nb), dim3(256), 0, s, E, H, (T*)dE, ldc, ps_r, gs, C, Hh, Ww, npix, ws, \
-                     eps)
-  if (charb) {
-    if (dtype == KAIR_BF16 && i32) KAIR_PIXEL_LOSS(bf16, int, true);
-    else if (dtype == KAIR_BF16) KAIR_PIXEL_LOSS(bf16, long, true);
-    else if (i32) KAIR_PIXEL_LOSS(float, int, true);
-    else KAIR_PIXEL_LOSS(float, long, true);
-  } else {
-    if (dtype == KAIR_BF16 && i32) KAIR_PIXEL_LOSS(bf16, int, false);
-    else if (dtype == KAIR_BF16) KAIR_PIXEL_LOSS(bf16, long, false);
-    else if (i32) KAIR_PIXEL_LOSS(float, int, false);
-    else KAIR_PIXEL_LOSS(float, long, false);
-  }
+#define KAIR_PIXEL_LOSS(T, I, M)                                                                                         \
+  KAIR_LAUNCH((l1_kernel<T, I, M>), dim3(nb), dim3(256), 0, s, E, H, (T*)dE, ldc, ps_r, gs, C, Hh, Ww, npix, ws, eps)
+#define KAIR_PIXEL_LOSS_MODE(M)                                                                                          \
+  do {                                                                                                                   \
+    if (dtype == KAIR_BF16 && i32) KAIR_PIXEL_LOSS(bf16, int, M);                                                        \
+    else if (dtype == KAIR_BF16) KAIR_PIXEL_LOSS(bf16, long, M);                                                         \
+    else if (i32) KAIR_PIXEL_LOSS(float, int, M);                                                                        \
+    else KAIR_PIXEL_LOSS(float, long, M);                                                                                \
+  } while (0)
+  if (mode == LOSS_CHARB) KAIR_PIXEL_LOSS_MODE(LOSS_CHARB);
+  else if (mode == LOSS_L2) KAIR_PIXEL_LOSS_MODE(LOSS_L2);
+  else KAIR_PIXEL_LOSS_MODE(LOSS_L1);
+#undef KAIR_PIXEL_LOSS_MODE
 #undef KAIR_PIXEL_LOSS
   KAIR_CHECK_LAUNCH();
-  KAIR_LAUNCH(l1_final, dim3(1), dim3(256), 0, s, ws, nb, (float)(weight / numel), loss_out);
+  KAIR_LAUNCH(l1_final, dim3(1), dim3(256), 0, s, ws, nb, (float)wn, loss_out);
   KAIR_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int kair_l1_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r,
                             float weight, int B, int C, int Hh, int Ww, float* ws, void* stream) {
-  return pixel_loss(E, H, loss_out, dE, dtype, ldc, ps_r, weight, 0.f, false, B, C, Hh, Ww, ws, stream);
+  return pixel_loss("pixel loss", E, H, loss_out, dE, dtype, ldc, ps_r, weight, 0.f, LOSS_L1, false, B, C, Hh, Ww, ws,
+                    stream);
 }
 
 extern "C" int kair_charbonnier_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc,
                                      int ps_r, float weight, float eps, int B, int C, int Hh, int Ww, float* ws,
                                      void* stream) {
   KAIR_CHECK_ARG(eps >= 0.f, "charbonnier_loss: eps must be >= 0");
-  return pixel_loss(E, H, loss_out, dE, dtype, ldc, ps_r, weight, eps, true, B, C, Hh, Ww, ws, stream);
+  return pixel_loss("pixel loss", E, H, loss_out, dE, dtype, ldc, ps_r, weight, eps, LOSS_CHARB, false, B, C, Hh, Ww, ws,
+                    stream);
+}
+
+extern "C" int kair_l2_loss(const float* E, const float* H, float* loss_out, void* dE, int dtype, int ldc, int ps_r,
+                            float weight, int sum_reduction, int B, int C, int Hh, int Ww, float* ws, void* stream) {
+  KAIR_CHECK_ARG(dtype == KAIR_F32 || dtype == KAIR_BF16, "l2_loss: dE dtype %d (fp32 or bf16)", dtype);
+  KAIR_CHECK_ARG(B > 0 && C > 0 && Hh > 0 && Ww > 0, "l2_loss: bad sizes (B %d, C %d, %dx%d)", B, C, Hh, Ww);
+  return pixel_loss("l2_loss", E, H, loss_out, dE, dtype, ldc, ps_r, weight, 0.f, LOSS_L2, sum_reduction != 0, B, C, Hh,
+                    Ww, ws, stream);
 }
 
 extern "C" int kair_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t,
@@ -1260,6 +1372,37 @@ extern "C" int kair_adam_ema_ex(float* p, const float* g, float* m, float* v, fl
   if (nb > 8192) nb = 8192;
   KAIR_LAUNCH(adam_ema_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr_t,
                      beta1, beta2, eps, weight_decay, ema_decay, skip);
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kair_adam_ema_clip(float* p, float* g, float* m, float* v, float* ema, long n, const float* lr_t,
+                                  float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                                  const unsigned* skip, const float* gnorm, float max_norm, void* stream) {
+  KAIR_CHECK_ARG(p && g && m && v && lr_t && n > 0, "adam_ema_clip: bad args");
+  KAIR_CHECK_ARG(gnorm, "adam_ema_clip: null gnorm");
+  KAIR_CHECK_ARG(max_norm > 0.f, "adam_ema_clip: max_norm must be > 0");
+  long nb = (n + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  KAIR_LAUNCH(adam_ema_clip_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr_t,
+                     beta1, beta2, eps, weight_decay, ema_decay, skip, gnorm, max_norm);
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" long kair_grad_norm_ws(int* grid, int* block) {
+  if (grid) *grid = GN_GRID;
+  if (block) *block = GN_BLOCK;
+  return GN_GRID;
+}
+
+extern "C" int kair_grad_norm(const float* g, long n, float* ws, float* norm_out, void* stream) {
+  KAIR_CHECK_ARG(g && ws && norm_out, "grad_norm: null pointer");
+  KAIR_CHECK_ARG(n > 0, "grad_norm: n must be > 0");
+  hipStream_t s = (hipStream_t)stream;
+  KAIR_LAUNCH(grad_norm_partial_kernel, dim3(GN_GRID), dim3(GN_BLOCK), 0, s, g, n, ws);
+  KAIR_CHECK_LAUNCH();
+  KAIR_LAUNCH(grad_norm_final_kernel, dim3(1), dim3(GN_BLOCK), 0, s, ws, norm_out);
   KAIR_CHECK_LAUNCH();
   return 0;
 }

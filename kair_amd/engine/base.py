@@ -237,8 +237,16 @@ class EngineBase:
     def _x3_grad_exp(self, numel, weight=1.0, loss_type=None):
         """The fp32x3 gradient exponent: the mean-loss gradient is O(weight / numel) per output element (weight: the
         loss weight over img_range), so data gradients times 2^(log2(numel / weight) + 4) sit near 2^4 at the loss,
-        2^12 below fp16's overflow.  'ssim': numel |dS/dE| is not bounded by 1 -- X3_SSIM_HEADROOM binades lower."""
+        2^12 below fp16's overflow.  'ssim': numel |dS/dE| is not bounded by 1 -- X3_SSIM_HEADROOM binades lower.
+        'l2': the gradient 2 weight (E - H) / numel is bounded by 2 |weight| / numel for images in [0, 1], twice
+        L1's |weight| / numel, so the same derivation gives L1's exponent less one binade and the bound sits at 2^4 as
+        L1's constant does (typical gradients, |E - H| << 1, lie below it).  'l2sum': no division by numel, the bound
+        is 2 |weight|: 'l2' at numel = 1.  The range guard stays the backstop."""
+        if loss_type == "l2sum":
+            numel = 1
         e = int(round(math.log2(max(numel, 1) / max(abs(weight), 1e-30)))) + self.x3_gexp_off
+        if loss_type in ("l2", "l2sum"):
+            return e - 1
         return e - self.X3_SSIM_HEADROOM if loss_type == "ssim" else e
 
     # numel |dS/dE| of the SSIM loss: <= ~4 / C2 + 1 / sqrt(C1) ~ 2^12 for images in [0, 1] (flat patches that differ
@@ -251,8 +259,8 @@ class EngineBase:
 
     def pixel_loss(self, P, E, H_img, dE, ldc, weight, C, Hh, Ww, ps_r=1, charb_eps=None, loss_type=None):
         """The one dispatch of every engine's loss hook: loss_type None / 'l1' / 'charbonnier' (charb_eps set) ->
-        kair_l1_loss / kair_charbonnier_loss; 'ssim' -> kair_ssim_loss, whose workspace joins the plan on the first
-        SSIM step (an eager warm-up step: before any capture), so L1 plans stay as they were.  Loss into P['loss'],
+        kair_l1_loss / kair_charbonnier_loss; 'l2' / 'l2sum' -> kair_l2_loss (mean / sum); 'ssim' -> kair_ssim_loss,
+        whose workspace joins the plan on the first SSIM step (an eager warm-up step: before any capture), so L1 plans stay as they were.  Loss into P['loss'],
         gradient rows into dE."""
         if loss_type == "ssim":
             ws = P.get("ssim_ws")
@@ -262,6 +270,9 @@ class EngineBase:
         elif loss_type in (None, "l1", "charbonnier"):
             H.l1_loss(E, H_img, P["loss"], dE, ldc, weight, P["B"], C, Hh, Ww, P["loss_ws"], ps_r=ps_r,
                       charb_eps=charb_eps)
+        elif loss_type in ("l2", "l2sum"):
+            H.l2_loss(E, H_img, P["loss"], dE, ldc, weight, P["B"], C, Hh, Ww, P["loss_ws"], ps_r=ps_r,
+                      reduction="sum" if loss_type == "l2sum" else "mean")
         else:
             raise NotImplementedError(f"fused pixel loss {loss_type!r}")
 

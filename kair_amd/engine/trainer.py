@@ -5,6 +5,7 @@ ModelBase.update_E (model_base.py:247-252) + the DDP reducer (model_base.py:113-
 
   forward (engine) -> L1 loss + dL/dE (kernel) -> backward (engine, grads written into ONE flat
   fp32 buffer) -> [RCCL all-reduce of the flat buffer, bucketed, divided by world size]
+  -> [clip_grad: the 2-norm of the flat gradient (kernel), read by the update on the device]
   -> fused Adam + EMA over the flat parameter / state buffers (one kernel)
 
 Parameters of netG (and netE) become views into flat fp32 buffers, so state_dict()/load_state_dict
@@ -68,7 +69,7 @@ def segment_buckets(params, segs):
 class FusedTrainer:
     def __init__(self, netG, netE=None, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, E_decay=0.999,
                  loss_weight=1.0, use_graph=True, process_group=None, bucket_mb=25, segment_graphs=None, charb_eps=None,
-                 stream_priority=0, loss_type=None):
+                 stream_priority=0, loss_type=None, clip_grad=None):
         self.net, self.ema_net = netG, netE
         self.stream_priority = stream_priority   # torch priority of the capture stream (0: default)
         self.device = next(netG.parameters()).device
@@ -91,12 +92,25 @@ class FusedTrainer:
         # None: L1 (G_lossfn_type 'l1'); a float: the Charbonnier loss with that eps ('charbonnier')
         self.charb_eps = charb_eps
         # loss_type None: charb_eps decides as above; 'ssim': weight * mean SSIM (kair_ssim_loss; the SSIM itself, so a
-        # run that maximises it has a negative loss_weight)
-        if loss_type not in (None, "l1", "charbonnier", "ssim"):
+        # run that maximises it has a negative loss_weight); 'l2' / 'l2sum': weight * the mean / the sum of (E - H)^2
+        # (kair_l2_loss)
+        if loss_type not in (None, "l1", "l2", "l2sum", "charbonnier", "ssim"):
             raise NotImplementedError(f"FusedTrainer: loss_type {loss_type!r}")
         if loss_type == "charbonnier" and charb_eps is None:
             raise ValueError("FusedTrainer: loss_type 'charbonnier' needs charb_eps")
         self.loss_type = loss_type
+        # clip_grad (G_optimizer_clipgrad, model_plain.py:296-298): clip_grad_norm_ of all gradients to that 2-norm,
+        # on the device -- kair_grad_norm over the flat buffer (after the all-reduce and its 1 / world: the norm of the
+        # averaged gradient, the same on every rank, as DDP followed by clip_grad_norm_), then kair_adam_ema_clip, which
+        # also leaves the clipped gradient in flat_g.  gnorm: the pre-clip norm of the last step.  Both buffers exist
+        # before any capture.  None: the step's launches are what they were.
+        self.clip_grad = None if clip_grad is None else float(clip_grad)
+        self.gnorm = None
+        if self.clip_grad is not None:
+            if not self.clip_grad > 0:
+                raise ValueError(f"FusedTrainer: clip_grad must be > 0 (got {clip_grad!r})")
+            self.gnorm = torch.zeros(1, device=self.device)
+            self.gnorm_ws = torch.zeros(H.grad_norm_geometry()[2], device=self.device)
         self.t = 0
         self.scal = torch.zeros(2, device=self.device)
         self.pg = process_group
@@ -145,8 +159,8 @@ class FusedTrainer:
             eng.forward(L, *cond)
         else:
             eng.forward(L, drop)
-        if self.loss_type == "ssim":
-            return eng.backward_from_loss(Hh, self.grads, self.loss_weight, loss_type="ssim")
+        if self.loss_type in ("ssim", "l2", "l2sum"):
+            return eng.backward_from_loss(Hh, self.grads, self.loss_weight, loss_type=self.loss_type)
         return eng.backward_from_loss(Hh, self.grads, self.loss_weight,
                                       charb_eps=None if self.loss_type == "l1" else self.charb_eps)
 
@@ -157,6 +171,12 @@ class FusedTrainer:
             # rank drops and re-runs the same steps; a rank's own loss would not be)
             H.range_check(self.flat_g, self.flat_p, loss if self.world == 1 else None, self.p_limit, self.rflag)
             skip = self.rflag
+        if self.clip_grad is not None:
+            H.grad_norm(self.flat_g, self.gnorm_ws, self.gnorm)
+            H.adam_ema_clip(self.flat_p, self.flat_g, self.m, self.v, self.flat_e, self.flat_p.numel(), self.scal,
+                            self.betas[0], self.betas[1], self.eps, self.wd,
+                            self.E_decay if self.flat_e is not None else 0.0, self.gnorm, self.clip_grad, skip=skip)
+            return
         H.adam_ema(self.flat_p, self.flat_g, self.m, self.v, self.flat_e, self.flat_p.numel(), self.scal,
                    self.betas[0], self.betas[1], self.eps, self.wd, self.E_decay if self.flat_e is not None else 0.0,
                    skip=skip)

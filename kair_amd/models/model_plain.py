@@ -1,9 +1,9 @@
 """ModelPlain — pixel-loss trainer (mirror of /root/reference/models/model_plain.py:15-402).
 
 optimize_parameters keeps the reference order (zero_grad -> forward -> w*L1 -> backward -> Adam ->
-log G_loss -> EMA update_E) but, for networks with a fused MI355X engine and the 'l1' loss, runs it
-as ONE launch-only step captured in a HIP graph (kair_amd.engine.trainer.FusedTrainer): the grads
-land in a flat buffer, are all-reduced over RCCL when dist is on, and one kernel applies Adam +
+log G_loss -> EMA update_E) but, for networks with a fused MI355X engine (fused_step_supported:
+every pixel loss, with or without G_optimizer_clipgrad), runs it as ONE launch-only step captured
+in a HIP graph (kair_amd.engine.trainer.FusedTrainer): the grads land in a flat buffer, are all-reduced over RCCL when dist is on, and one kernel applies Adam +
 EMA.  The optimizer object is a torch.optim.Optimizer subclass whose state_dict() is torch Adam's
 format, so '{iter}_optimizerG.pth' interchanges with the reference; the scheduler is torch's
 MultiStepLR stepped before the optimizer step exactly as main_train_psnr.py:176 does.
@@ -17,6 +17,29 @@ from torch.optim import Adam, lr_scheduler
 from ..engine.trainer import FusedTrainer
 from .model_base import ModelBase
 from .select_network import define_G
+
+
+FUSED_LOSSES = ("l1", "l2", "l2sum", "charbonnier", "ssim")
+
+
+def fused_step_supported(opt_train):
+    """(ok, reason): whether the options' train section can run on the fused step (FusedTrainer), and if not, why.
+    Pure: the device and engine checks are ModelPlain._fused_ok's.  Every pixel loss of define_loss runs fused, with
+    or without G_optimizer_clipgrad (clipped inside the captured step).  Not fused: another optimizer than Adam,
+    either regularizer key (G_regularizer_orthstep / G_regularizer_clipstep: not built on either path), and
+    use_fused_trainer false -- the build-side switch (default true) that forces the autograd path, for A/B runs, the
+    way use_hip_graph false forces eager launches."""
+    if not opt_train.get("use_fused_trainer", True):
+        return False, "use_fused_trainer is false"
+    t = opt_train.get("G_lossfn_type")
+    if t not in FUSED_LOSSES:
+        return False, f"G_lossfn_type {t!r} has no fused loss kernel"
+    if opt_train.get("G_optimizer_type") != "adam":
+        return False, f"G_optimizer_type {opt_train.get('G_optimizer_type')!r}: the fused update is Adam"
+    for k in ("G_regularizer_orthstep", "G_regularizer_clipstep"):
+        if opt_train.get(k):
+            return False, f"{k} is set: the regularizers are not on the fused step"
+    return True, ""
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -253,22 +276,23 @@ class ModelPlain(ModelBase):
     def _fused_ok(self):
         net = self.get_bare_model(self.netG)
         return (hasattr(net, "engine") and self.device.type == "cuda" and all(p.requires_grad for p in net.parameters())
-                and self.G_lossfn_type in ("l1", "charbonnier", "ssim") and not self.opt_train.get("G_optimizer_clipgrad")
-                and self.opt_train["G_optimizer_type"] == "adam"
-                and not self.opt_train.get("G_regularizer_orthstep") and not self.opt_train.get("G_regularizer_clipstep"))
+                and fused_step_supported(self.opt_train)[0])
 
     def define_optimizer(self):
         params = [p for p in self.netG.parameters() if p.requires_grad]
         tr = self.opt_train
         if self._fused_ok():
             netE = self.netE if tr["E_decay"] > 0 else None
+            clip = tr.get("G_optimizer_clipgrad") or 0   # (> 0 clips, as optimize_parameters' autograd path)
             self.trainer = FusedTrainer(self.get_bare_model(self.netG), netE, lr=tr["G_optimizer_lr"],
                                         betas=tuple(tr["G_optimizer_betas"]), eps=1e-8,
                                         weight_decay=tr["G_optimizer_wd"], E_decay=tr["E_decay"],
                                         loss_weight=self.G_lossfn_weight,
                                         charb_eps=(tr.get("G_charbonnier_eps", 1e-9) if self.G_lossfn_type == "charbonnier"
                                                    else None),
-                                        loss_type="ssim" if self.G_lossfn_type == "ssim" else None,
+                                        loss_type=(self.G_lossfn_type if self.G_lossfn_type in ("ssim", "l2", "l2sum")
+                                                   else None),
+                                        clip_grad=clip if clip > 0 else None,
                                         use_graph=tr.get("use_hip_graph", True))
             self.G_optimizer = FusedAdam(self.trainer.params, self.trainer, tr["G_optimizer_lr"],
                                          tr["G_optimizer_betas"], 1e-8, tr["G_optimizer_wd"])
