@@ -588,6 +588,34 @@ int kair_ssim_loss(const float* E, const float* H, float* loss_out, void* dE, in
                    int B, int C, int Hh, int Ww, void* workspace, void* stream);
 int kair_ssim_loss_nchw(const float* E, const float* H, float* loss_out, float* dE, float weight, int B, int C, int Hh,
                         int Ww, void* workspace, void* stream);
+/* Evaluation metrics with the uint8 semantics of utils_image.py (tensor2uint -> calculate_psnr / calculate_ssim; not the
+ * SSIM loss above: no padding, data range 255, quantised input).  E, H: NCHW fp32 [B][C][Hh][Ww], C 1 or 3.  Per
+ * pixel q = rintf(__fmul_rn(clamp(x, 0, 1), 255.f)) (fp32 product, half to even); with KAIR_METRIC_Y (C = 3) the
+ * three channels become the one plane Y = 16 + round_half_even(N / 255000), N = 65481 r + 128553 g + 24966 b in
+ * integer quotient / remainder arithmetic (rgb2ycbcr(uint8, only_y) with its ties decided exactly); `border` pixels
+ * are cropped from every side.  out[b][0] = the sum of squared integer differences of image b over the cropped region
+ * and its planes (exact, as a double); with KAIR_METRIC_SSIM out[b][1] = the mean over planes of the mean SSIM map
+ * (11x11 Gaussian window, sigma 1.5, fully overlapping positions only, C1 = (0.01*255)^2, C2 = (0.03*255)^2; fp64
+ * moments and sums), else out[b][1] is left untouched.  One workgroup per 32x32 tile of a plane writes its integer SSE
+ * and its SSIM sum to its own 16-byte workspace slot; one workgroup adds the slots in a fixed order (no atomics:
+ * repeated calls are bit-identical).  Stream-ordered: no host synchronisation, no allocation.
+ * workspace: kair_image_metrics_workspace_bytes(...) bytes (0 for arguments the call rejects), 16-byte aligned.
+ * Argument errors (null pointer, C not 1 or 3, Y with C != 3, unknown flag bits, empty cropped region, a region smaller
+ * than 11 in either dimension with SSIM, misaligned workspace) launch nothing. */
+#define KAIR_METRIC_Y 1
+#define KAIR_METRIC_SSIM 2
+long kair_image_metrics_workspace_bytes(int B, int C, int H, int W, int border, int flags);
+int kair_image_metrics(const float* E, const float* H, double* out, int B, int C, int Hh, int Ww, int border, int flags,
+                       void* workspace, void* stream);
+/* calculate_psnr's dB from exact SSEs with the host's bits: db[i*ldd] = 20*log10(255 / sqrt(sse[i*lds] / count)) in
+ * float64, inf where the SSE is 0; n values, count = the number of compared values per image; db may be sse (in
+ * place).  Division and square root are IEEE; the log10 is fdlibm's e_log10 formula (what the host C library
+ * computes), every operation rounded on its own, around a correctly rounded log (double-double atanh series): the
+ * host's value bit for bit except where the host's own log is misrounded (about 1 value in 2000 with glibc 2.35).
+ * kair_psnr_db_ref evaluates the same source on the host (no device needed).  Argument errors (null pointer, n, a
+ * stride or count < 1) launch nothing. */
+int kair_psnr_db(const double* sse, long lds, double* db, long ldd, int n, double count, void* stream);
+double kair_psnr_db_ref(double sse, double count);
 /* y[i] += a * x[i] over n fp32 elements (residual-gradient merges). */
 int kair_axpy(float* y, const float* x, float a, long n, void* stream);
 /* BatchNorm2d over NHWC rows z [M, C] fp32 (basicblock.py:69: momentum 0.9, eps 1e-4), fused act

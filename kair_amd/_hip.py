@@ -180,6 +180,10 @@ _SIGS = {
     "kair_ssim_workspace_bytes": [c_int, c_int, c_int, c_int],
     "kair_ssim_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp],
     "kair_ssim_loss_nchw": [c_vp, c_vp, c_vp, c_vp, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_image_metrics_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "kair_image_metrics": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp],
+    "kair_psnr_db": [c_vp, c_long, c_vp, c_long, c_int, ctypes.c_double, c_vp],
+    "kair_psnr_db_ref": [ctypes.c_double, ctypes.c_double],
     "kair_charbonnier_loss": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int,
                               c_vp, c_vp],
     "kair_axpy": [c_vp, c_vp, c_float, c_long, c_vp],
@@ -271,7 +275,8 @@ _RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": 
             "kair_pack_table_build": c_long, "kair_conv3x3_narrow_wgrad_ws": c_long,
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
             "kair_jpeg_workspace_bytes": c_long, "kair_ssim_workspace_bytes": c_long,
-            "kair_grad_norm_ws": c_long}
+            "kair_grad_norm_ws": c_long, "kair_image_metrics_workspace_bytes": c_long,
+            "kair_psnr_db_ref": ctypes.c_double}
 
 _lib = None
 
@@ -847,6 +852,46 @@ def ssim_loss(E, H, loss_out, dE, ldc, weight, B, C, Hh, Ww, ws, ps_r=1):
         return
     check(lib().kair_ssim_loss(ptr(E), ptr(H), ptr(loss_out), ptr(dE), dtype_code(dE), ldc, ps_r, weight, B, C, Hh, Ww,
                                ptr(ws), stream_ptr()), "ssim_loss")
+
+
+METRIC_Y, METRIC_SSIM = 1, 2   # KAIR_METRIC_Y, KAIR_METRIC_SSIM
+
+
+def image_metrics_workspace(B, C, Hh, Ww, border, flags, device):
+    """The workspace of one image_metrics call (kair_image_metrics_workspace_bytes: one 16-byte slot per tile)."""
+    nbytes = lib().kair_image_metrics_workspace_bytes(B, C, Hh, Ww, border, flags)
+    if nbytes <= 0:
+        raise ValueError(f"kair_image_metrics: no valid call on [{B}, {C}, {Hh}, {Ww}] images with border {border}, "
+                         f"flags {flags}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def image_metrics(E, H, out, B, C, Hh, Ww, border, flags, ws):
+    """kair_image_metrics: per image the exact uint8 SSE (out[b][0]) and, with METRIC_SSIM, the uint8 SSIM (out[b][1])
+    of fp32 NCHW images; METRIC_Y: on the Y channel (C = 3).  out: float64 [B, 2]; ws: image_metrics_workspace(...)."""
+    require_device(E, H, out, ws)
+    if out.dtype != torch.float64 or out.numel() < 2 * B:
+        raise TypeError("kair_image_metrics: out is a float64 [B, 2] tensor")
+    need = lib().kair_image_metrics_workspace_bytes(B, C, Hh, Ww, border, flags)
+    if ws.numel() * ws.element_size() < need:
+        raise ValueError(f"kair_image_metrics: workspace too small ({ws.numel() * ws.element_size()} < {need} bytes)")
+    check(lib().kair_image_metrics(ptr(E), ptr(H), ptr(out), B, C, Hh, Ww, border, flags, ptr(ws), stream_ptr()),
+          "image_metrics")
+
+
+def psnr_db(sse, db, count):
+    """kair_psnr_db: db[i] = calculate_psnr's dB of the exact SSE sse[i] over `count` compared values (inf at 0), with
+    the host C library's bits.  sse, db: float64 device tensors of one dimension (any stride; db may be sse)."""
+    require_device(sse, db)
+    if sse.dtype != torch.float64 or db.dtype != torch.float64 or sse.dim() != 1 or db.shape != sse.shape:
+        raise TypeError("kair_psnr_db: sse and db are float64 vectors of one length")
+    check(lib().kair_psnr_db(ptr(sse), max(1, sse.stride(0)), ptr(db), max(1, db.stride(0)), sse.numel(), float(count),
+                             stream_ptr()), "psnr_db")
+
+
+def psnr_db_ref(sse, count):
+    """kair_psnr_db_ref: the same arithmetic evaluated on the host for one value."""
+    return lib().kair_psnr_db_ref(float(sse), float(count))
 
 
 def axpy(y, x, a, n=None):

@@ -362,6 +362,14 @@ class ModelPlain(ModelBase):
             self.E = test_mode(self.netG, self.L, mode=3, sf=self.opt["scale"], modulo=1)
         self.netG.train()
 
+    def test_metrics(self, border=0, y_channel=False, ssim=True):
+        """uint8 (PSNR dB, SSIM) of self.E against self.H after test() / testx8(): a float64 tensor [B, 2] on the
+        model's device (utils_image.tensor_metrics; kair_image_metrics on the GPU, nothing read back)."""
+        from ..utils.utils_image import tensor_metrics
+        if getattr(self, "E", None) is None or getattr(self, "H", None) is None:
+            raise RuntimeError("test_metrics: run feed_data (with H) and test() first")
+        return tensor_metrics(self.E, self.H, border=border, y_channel=y_channel, ssim=ssim)
+
     def current_log(self):
         return self.log_dict
 

@@ -331,3 +331,82 @@ def calculate_ssim(img1, img2, border=0):
         if a.shape[2] == 1:
             return ssim(np.squeeze(a), np.squeeze(b))
     raise ValueError("Wrong input image dimensions.")
+
+
+# ------------------------------------------------------------------------------------------
+# tensor-level evaluation metrics (the uint8 PSNR / SSIM above, on the device through kair_image_metrics)
+# ------------------------------------------------------------------------------------------
+def rgb2y_uint8(img):
+    """Y of rgb2ycbcr(uint8 HxWx3 (or ...x3), only_y=True) in exact integer arithmetic: with N = 65481 r + 128553 g +
+    24966 b, Y = 16 + round_half_even(N / 255000) from the integer quotient and remainder.  The float64 np.dot of
+    rgb2ycbcr differs from it only at exact ties N = 127500 (mod 255000): 194 of the 2^24 triples, 24 of which numpy
+    rounds the other way, by one level.  This rule is what the device kernel computes."""
+    if img.dtype != np.uint8 or img.shape[-1] != 3:
+        raise ValueError("rgb2y_uint8 takes a uint8 array of RGB triples")
+    x = img.astype(np.int64)
+    n = 65481 * x[..., 0] + 128553 * x[..., 1] + 24966 * x[..., 2]
+    q, rem = n // 255000, n % 255000
+    q = q + ((rem > 127500) | ((rem == 127500) & (q % 2 == 1)))
+    return (16 + q).astype(np.uint8)
+
+
+def _tensor2uint_hwc(img):
+    """[C, H, W] float tensor -> uint8 HxW (C = 1) or HxWxC with tensor2uint's arithmetic, whatever H and W are
+    (tensor2uint squeezes, so it is applied per channel plane and the shape restored)."""
+    C, H, W = img.shape
+    planes = [tensor2uint(img[c]).reshape(H, W) for c in range(C)]
+    return planes[0] if C == 1 else np.stack(planes, axis=2)
+
+
+def tensor_metrics(E, H, border=0, y_channel=False, ssim=True):
+    """Per-image uint8 (PSNR dB, SSIM) of float images E, H ([B, C, H, W] or [C, H, W], C 1 or 3, any float dtype, any
+    strides) as a float64 tensor [B, 2] on the images' device: tensor2uint's quantisation, optionally the Y channel
+    (C = 3; rgb2y_uint8's integer rule), `border` pixels cropped from every side, then calculate_psnr and
+    calculate_ssim.  PSNR is inf for identical images; with ssim=False column 1 is NaN.
+
+    Device tensors: one kair_image_metrics call (csrc/metrics.hip) and kair_psnr_db, which turns the exact SSE into dB
+    with the host C library's log10 arithmetic (torch.log10 on the device differs from it in the last place on every
+    fifth value); nothing is read back, so a validation loop can collect the results and synchronise once.  CPU
+    tensors: the host functions of this file per image."""
+    if not (torch.is_tensor(E) and torch.is_tensor(H)):
+        raise TypeError("tensor_metrics takes tensors")
+    if E.shape != H.shape:
+        raise ValueError(f"tensor_metrics: E {tuple(E.shape)} and H {tuple(H.shape)} differ in shape")
+    if E.device != H.device:
+        raise ValueError(f"tensor_metrics: E on {E.device}, H on {H.device}")
+    if E.dim() == 3:
+        E, H = E.unsqueeze(0), H.unsqueeze(0)
+    if E.dim() != 4:
+        raise ValueError(f"tensor_metrics: images are [B, C, H, W] or [C, H, W] (got {E.dim()} dimensions)")
+    if not (E.is_floating_point() and H.is_floating_point()):
+        raise TypeError("tensor_metrics: float images in [0, 1]")
+    B, C, Hh, Ww = E.shape
+    border = int(border)
+    if C not in (1, 3):
+        raise ValueError(f"tensor_metrics: C = {C} (1 or 3)")
+    if y_channel and C != 3:
+        raise ValueError(f"tensor_metrics: the Y channel needs C = 3 (got {C})")
+    hr, wr = Hh - 2 * border, Ww - 2 * border
+    if B < 1 or border < 0 or hr < 1 or wr < 1:
+        raise ValueError(f"tensor_metrics: border {border} leaves no pixel of {B} x {Hh} x {Ww}")
+    if ssim and (hr < 11 or wr < 11):
+        raise ValueError(f"tensor_metrics: the SSIM window is 11 x 11, the cropped region {hr} x {wr}")
+    E, H = E.detach().float().contiguous(), H.detach().float().contiguous()
+    if E.is_cuda:
+        from .. import _hip
+        flags = (_hip.METRIC_Y if y_channel else 0) | (_hip.METRIC_SSIM if ssim else 0)
+        out = torch.full((B, 2), float("nan"), dtype=torch.float64, device=E.device)
+        ws = _hip.image_metrics_workspace(B, C, Hh, Ww, border, flags, E.device)
+        _hip.image_metrics(E, H, out, B, C, Hh, Ww, border, flags, ws)
+        # SSE -> dB in place (inf at 0): kair_psnr_db reproduces the host's log10, which torch.log10 on the device does not
+        _hip.psnr_db(out[:, 0], out[:, 0], hr * wr * (1 if y_channel else C))
+        return out
+    out = torch.full((B, 2), float("nan"), dtype=torch.float64)
+    for b in range(B):
+        e, h = _tensor2uint_hwc(E[b]), _tensor2uint_hwc(H[b])
+        if y_channel:
+            e, h = rgb2y_uint8(e), rgb2y_uint8(h)
+        out[b, 0] = calculate_psnr(e, h, border=border)
+        if ssim:
+            out[b, 1] = float(calculate_ssim(e, h, border=border))
+    return out
