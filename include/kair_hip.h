@@ -284,7 +284,10 @@ int kair_colsum(const kair_operand* G, long M, int Np, const kair_wmap* map, flo
 
 /* LayerNorm over the last dim (nn.LayerNorm eps 1e-5; network_swinir.py:199,205,520,725).
  * x fp32 [M, ldx] token order -> y (dtype) at rows rowmap^-1 (window order when win_ws > 0),
- * y pad columns [C, ldy) written 0.  mean/rstd fp32 [M] indexed by token row. */
+ * y pad columns [C, ldy) written 0.  mean/rstd fp32 [M] indexed by token row.
+ * C <= 256, ldx >= C, C <= ldy <= 256, both strides multiples of 4; one_col < 0 or a pad column [C, ldy), which
+ * then reads 1.  With a map (win_ws > 0) win_H and win_W are multiples of win_ws and M is a multiple of
+ * win_H * win_W (whole images: the map addresses no other row count); anything else is KAIR_ERR_ARG. */
 int kair_layernorm_fwd(const float* x, long ldx, void* y, int y_dtype, long ldy, const float* gamma,
                        const float* beta, float* mean, float* rstd, long M, int C, float eps,
                        int win_H, int win_W, int win_ws, int win_shift, int one_col, void* stream);
@@ -309,8 +312,11 @@ typedef struct {
 int kair_row_copy(const float* src, long ld_src, long M, int C, const kair_copy_desc* copy, void* stream);
 
 /* dx_acc[t] (+)= LN-backward(dy) for token rows t; dgamma/dbeta (+)= column sums.
- * dy (dtype) is addressed like y in the forward.  ws: 2 * 2048 * C floats.
- * copy (optional): also write the finished dx rows as a kair_copy_desc. */
+ * dy (dtype) is addressed like y in the forward.  ws: 2 * 2048 * C floats
+ * (kair_layernorm_bwd_blocks(M) * 2 * C of them are written).
+ * copy (optional): also write the finished dx rows as a kair_copy_desc.
+ * ldx, ldy, ld_dx and copy->ld are >= C and multiples of 4; the main map and the copy's map each follow the
+ * forward's rule (win_H, win_W multiples of win_ws, M a multiple of win_H * win_W), else KAIR_ERR_ARG. */
 int kair_layernorm_bwd(const float* x, long ldx, const void* dy, int dy_dtype, long ldy,
                        const float* gamma, const float* mean, const float* rstd, float* dx_acc,
                        long ld_dx, int dx_accumulate, float* dgamma, float* dbeta, int dparam_accumulate,

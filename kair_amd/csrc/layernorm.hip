@@ -407,6 +407,12 @@ __global__ __launch_bounds__(256) void ln_param_reduce_grouped(const LnParamGrou
 
 constexpr int LN_BLOCKS = 2048;
 
+// a window map addresses whole images of whole windows: with any other M, win_to_token / token_to_win return rows
+// past M
+static bool ln_map_rows_ok(long M, int win_H, int win_W, int win_ws) {
+  return win_ws == 0 || (win_H > 0 && win_W > 0 && M % ((long)win_H * win_W) == 0);
+}
+
 static long ln_bwd_blocks(long M) {
   long nb = (M + ROWS_PER_BLOCK_ITER - 1) / ROWS_PER_BLOCK_ITER;
   return nb > LN_BLOCKS ? LN_BLOCKS : nb;
@@ -440,6 +446,7 @@ extern "C" int kair_layernorm_fwd(const float* x, long ldx, void* y, int y_dtype
                  "layernorm_fwd: bad sizes");
   KAIR_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % 16) == 0, "layernorm_fwd: strides must be multiples of 4");
   KAIR_CHECK_ARG(win_ws == 0 || (win_H % win_ws == 0 && win_W % win_ws == 0), "layernorm_fwd: window geometry");
+  KAIR_CHECK_ARG(ln_map_rows_ok(M, win_H, win_W, win_ws), "layernorm_fwd: M must be whole win_H x win_W images");
   KAIR_CHECK_ARG(one_col < 0 || (one_col >= C && one_col < ldy), "layernorm_fwd: ones column must be a pad column");
   const WinMap wm = make_winmap(win_H, win_W, win_ws, win_shift);
   long nb = (M + ROWS_PER_BLOCK_ITER - 1) / ROWS_PER_BLOCK_ITER;
@@ -468,6 +475,7 @@ extern "C" int kair_layernorm_fwd_x3(const float* x, long ldx, void* y_hi, void*
                      ((uintptr_t)y_lo % 8) == 0,
                  "layernorm_fwd_x3: strides / alignment");
   KAIR_CHECK_ARG(win_ws == 0 || (win_H % win_ws == 0 && win_W % win_ws == 0), "layernorm_fwd_x3: window geometry");
+  KAIR_CHECK_ARG(ln_map_rows_ok(M, win_H, win_W, win_ws), "layernorm_fwd_x3: M must be whole win_H x win_W images");
   KAIR_CHECK_ARG(one_col < 0 || (one_col >= C && one_col < ldy), "layernorm_fwd_x3: ones column must be a pad column");
   KAIR_CHECK_ARG(x3_exp > -100 && x3_exp < 100, "layernorm_fwd_x3: exponent");
   const WinMap wm = make_winmap(win_H, win_W, win_ws, win_shift);
@@ -486,8 +494,11 @@ extern "C" int kair_layernorm_bwd(const float* x, long ldx, const void* dy, int 
                                   void* stream) {
   KAIR_CHECK_ARG(x && dy && gamma && mean && rstd && dx_acc && ws && (dgamma != nullptr) == (dbeta != nullptr),
                  "layernorm_bwd: null pointer");
-  KAIR_CHECK_ARG(C > 0 && C <= 256 && M > 0 && M < KAIR_MAX_MAPPED_ROWS, "layernorm_bwd: bad sizes");
+  KAIR_CHECK_ARG(C > 0 && C <= 256 && ldx >= C && ldy >= C && ld_dx >= C && M > 0 && M < KAIR_MAX_MAPPED_ROWS,
+                 "layernorm_bwd: bad sizes");
   KAIR_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ld_dx % 4 == 0, "layernorm_bwd: strides must be multiples of 4");
+  KAIR_CHECK_ARG(win_ws == 0 || (win_H % win_ws == 0 && win_W % win_ws == 0), "layernorm_bwd: window geometry");
+  KAIR_CHECK_ARG(ln_map_rows_ok(M, win_H, win_W, win_ws), "layernorm_bwd: M must be whole win_H x win_W images");
   const WinMap wm = make_winmap(win_H, win_W, win_ws, win_shift);
   void* cp = nullptr;
   f16* cp_lo = nullptr;
@@ -500,6 +511,8 @@ extern "C" int kair_layernorm_bwd(const float* x, long ldx, const void* dy, int 
     KAIR_CHECK_ARG(copy->ld % 4 == 0 && copy->ld >= C, "layernorm_bwd: copy stride");
     KAIR_CHECK_ARG(copy->win_ws == 0 || (copy->win_H % copy->win_ws == 0 && copy->win_W % copy->win_ws == 0),
                    "layernorm_bwd: copy window geometry");
+    KAIR_CHECK_ARG(ln_map_rows_ok(M, copy->win_H, copy->win_W, copy->win_ws),
+                   "layernorm_bwd: M must be whole images of the copy's win_H x win_W");
     cp = copy->out; cp_dt = copy->dtype; ldc = copy->ld; cp_scale = copy->rowscale;
     cp_rps = copy->rows_per_scale > 0 ? copy->rows_per_scale : 1;
     cwm = make_winmap(copy->win_H, copy->win_W, copy->win_ws, copy->win_shift);
