@@ -717,7 +717,9 @@ int kair_gate_release(void);
 int kair_gate_status(void);
 
 /* USRNet (network_usrnet_v1.py) -------------------------------------------------------------
- * Complex plane sets are float2 [planes][W][H] (TRANSPOSED: column-major per plane).            */
+ * Complex plane sets are float2 [planes][W][H] (TRANSPOSED: column-major per plane).
+ * H and W: any length in [2, 2048] (radix 4/2/3/5/7 butterflies, a p-term stage for every other prime
+ * factor: a prime length costs O(n^2) per line); outside that range KAIR_ERR_ARG.                 */
 #define KAIR_USR_SRC_NCHW 0  /* fp32 NCHW planes [planes][H][W]                                    */
 #define KAIR_USR_SRC_PSF 1   /* p2o of a PSF [B][1][kh][kw]: zero-pad + circular shift (v1:48-69)  */
 #define KAIR_USR_SRC_ZUP 2   /* s-fold zero-upsample of LQ planes [planes][H/sf][W/sf] (v1:72-82)   */

@@ -14,8 +14,9 @@
 //                                mean is CTA-local -> DFT along u -> closed form -> inverse DFT
 //                                along u -> lines written back;
 //   irows (kair_usr_ifft_rows) : R-row segments -> inverse DFT along v -> real part * scale.
-// Line DFTs are Stockham autosort (radix 4/2/3, any N = 2^a 3^b <= 2048) ping-ponging between two
-// LDS buffers; twiddles come from a per-CTA LDS table computed in double precision.
+// Line DFTs are Stockham autosort, any 2 <= N <= 2048, ping-ponging between two LDS buffers: register
+// butterflies of radix 4/2/3/5/7 and a generic stage for every other prime factor (one thread per
+// output, a p-term sum).  Twiddles come from a per-CTA LDS table computed in double precision.
 //
 // DataNet maths (per batch element b; B = FB, C = conj(FB), w = mean_alias |FB|^2, d = 1/(w+a)):
 //   FR = FBFy + a * F(x),  FX = (FR - C * T(S(B*FR)) * d) / a,  z = Re(F^-1(FX))
@@ -32,10 +33,11 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // Stockham line DFTs in LDS
 // ------------------------------------------------------------------------------------------
+constexpr int FFT_MAX_STAGES = 11;   // 2^11 = 2048: no length has more prime factors
 struct FftPlan {
-  int n;    // line length
-  int nst;  // stages
-  int enc;  // 2 bits per stage: 0 -> radix 2, 1 -> radix 3, 2 -> radix 4
+  int n;                                // line length
+  int nst;                              // stages
+  unsigned short radix[FFT_MAX_STAGES]; // per stage, in execution order: 4, 2, 3, 5, 7 or any other prime
 };
 
 KAIR_DEV float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -69,7 +71,44 @@ KAIR_DEV void dft_small(float2 (&v)[R]) {
     v[0] = cadd(v[0], t1);
     if (INV) { v[1] = cadd(m, r); v[2] = csub(m, r); }
     else { v[1] = csub(m, r); v[2] = cadd(m, r); }
+  } else if constexpr (R == 5) {
+    // X0 = v0 + t1 + t2, X(1,4) = m1 -/+ i n1, X(2,3) = m2 -/+ i n2 (forward; signs swap for the inverse)
+    const float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;   // cos(2 pi j / 5)
+    const float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;    // sin(2 pi j / 5)
+    const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]);
+    const float2 t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
+    const float2 m1 = make_float2(v[0].x + c1 * t1.x + c2 * t2.x, v[0].y + c1 * t1.y + c2 * t2.y);
+    const float2 m2 = make_float2(v[0].x + c2 * t1.x + c1 * t2.x, v[0].y + c2 * t1.y + c1 * t2.y);
+    const float2 n1 = mul_i(make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y));
+    const float2 n2 = mul_i(make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y));
+    v[0] = cadd(v[0], cadd(t1, t2));
+    if (INV) { v[1] = cadd(m1, n1); v[4] = csub(m1, n1); v[2] = cadd(m2, n2); v[3] = csub(m2, n2); }
+    else { v[1] = csub(m1, n1); v[4] = cadd(m1, n1); v[2] = csub(m2, n2); v[3] = cadd(m2, n2); }
+  } else if constexpr (R == 7) {
+    // X_k = v0 + sum_j cos(2 pi j k / 7) t_j -/+ i sum_j sin(2 pi j k / 7) d_j,  X_(7-k) the other sign
+    const float c1 = 0.62348980185873353f, c2 = -0.22252093395631440f, c3 = -0.90096886790241913f;
+    const float s1 = 0.78183148246802981f, s2 = 0.97492791218182361f, s3 = 0.43388373911755812f;
+    const float2 t1 = cadd(v[1], v[6]), t2 = cadd(v[2], v[5]), t3 = cadd(v[3], v[4]);
+    const float2 d1 = csub(v[1], v[6]), d2 = csub(v[2], v[5]), d3 = csub(v[3], v[4]);
+    auto mix = [](float2 z, float a, float2 p, float b, float2 q, float c, float2 r) {
+      return make_float2(z.x + a * p.x + b * q.x + c * r.x, z.y + a * p.y + b * q.y + c * r.y);
+    };
+    const float2 z0 = make_float2(0.f, 0.f);
+    const float2 m1 = mix(v[0], c1, t1, c2, t2, c3, t3), n1 = mul_i(mix(z0, s1, d1, s2, d2, s3, d3));
+    const float2 m2 = mix(v[0], c2, t1, c3, t2, c1, t3), n2 = mul_i(mix(z0, s2, d1, -s3, d2, -s1, d3));
+    const float2 m3 = mix(v[0], c3, t1, c1, t2, c2, t3), n3 = mul_i(mix(z0, s3, d1, -s1, d2, s2, d3));
+    v[0] = cadd(cadd(v[0], t1), cadd(t2, t3));
+    if (INV) {
+      v[1] = cadd(m1, n1); v[6] = csub(m1, n1);
+      v[2] = cadd(m2, n2); v[5] = csub(m2, n2);
+      v[3] = cadd(m3, n3); v[4] = csub(m3, n3);
+    } else {
+      v[1] = csub(m1, n1); v[6] = cadd(m1, n1);
+      v[2] = csub(m2, n2); v[5] = cadd(m2, n2);
+      v[3] = csub(m3, n3); v[4] = cadd(m3, n3);
+    }
   } else {
+    static_assert(R == 4, "dft_small: radix");
     const float2 s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]);
     const float2 s13 = cadd(v[1], v[3]), d13 = csub(v[1], v[3]);
     const float2 r = INV ? mul_i(d13) : mul_negi(d13);
@@ -108,15 +147,66 @@ KAIR_DEV void fft_stage(const float2* __restrict__ src, float2* __restrict__ dst
   }
 }
 
-// full DFT of nl lines; returns the buffer holding the result (a or b).  Ends with a barrier.
+// one Stockham stage of any radix p (the prime factors without a register butterfly): src -> dst.
+// One thread per output element.  Output (q, k, ro) of line l is
+//   sum_{r < p} src[j + r * nb] * tw[(r * (ro * n / p + k * tstep)) mod n],   j = q * Ns + k, nb = n / p,
+// the stage twiddle and the p-point DFT factor in one table entry.  The index advances by a fixed step
+// and wraps by a compare-and-subtract, so every phase is an entry of the double-precision table.  The
+// sum is kept in double: a prime line (n = p = 2039) is one 2039-term stage, and the fp32 products are
+// exact in double, so the result is rounded once however long the sum is.
+// LDS: threads are ordered j-fastest, so a wave reads src at consecutive float2 for each r (with nb = 1,
+// one broadcast address) and writes runs of Ns consecutive outputs; the table reads are strided by the
+// thread's step, which is as spread as the radix's residues are.  No LDS beyond the two line buffers.
 template <bool INV>
+KAIR_DEV void fft_stage_generic(const float2* __restrict__ src, float2* __restrict__ dst, int nl, int n, int ls, int Ns,
+                                int p, const float2* __restrict__ tw) {
+  const int nb = n / p;
+  const int tstep = n / (Ns * p);
+  const FDiv dn{n, 1.0f / (float)n}, dnb{nb, 1.0f / (float)nb}, dns{Ns, 1.0f / (float)Ns};
+  const int total = nl * n;
+  for (int i = threadIdx.x; i < total; i += blockDim.x) {
+    const int l = fdiv(i, dn), o = i - l * n;
+    const int ro = fdiv(o, dnb), j = o - ro * nb;
+    const int q = fdiv(j, dns), k = j - q * Ns;
+    int step = ro * nb + k * tstep;   // < n + nb
+    if (step >= n) step -= n;
+    const float2* s = src + l * ls + j;
+    double ax = 0.0, ay = 0.0;
+    int t = 0;
+    for (int r = 0; r < p; ++r) {
+      const float2 v = s[r * nb];
+      const float2 w = tw[t];
+      const double wy = INV ? -(double)w.y : (double)w.y;
+      ax += (double)v.x * (double)w.x - (double)v.y * wy;
+      ay += (double)v.x * wy + (double)v.y * (double)w.x;
+      t += step;
+      if (t >= n) t -= n;
+    }
+    dst[l * ls + q * Ns * p + k + ro * Ns] = make_float2((float)ax, (float)ay);
+  }
+}
+
+// full DFT of nl lines; returns the buffer holding the result (a or b).  Ends with a barrier.
+// ANY = false: plans of radix 4 / 2 / 3 only (lengths 2^a 3^b), the kernels' original instantiation -- the
+// wider stages would otherwise cost every length their scalar registers; ANY = true: every radix.
+template <bool INV, bool ANY>
 KAIR_DEV float2* fft_lines(float2* a, float2* b, int nl, int ls, const FftPlan& p, const float2* tw) {
   int Ns = 1;
   for (int s = 0; s < p.nst; ++s) {
-    const int code = (p.enc >> (2 * s)) & 3;
-    if (code == 2) { fft_stage<4, INV>(a, b, nl, p.n, ls, Ns, tw); Ns *= 4; }
-    else if (code == 0) { fft_stage<2, INV>(a, b, nl, p.n, ls, Ns, tw); Ns *= 2; }
-    else { fft_stage<3, INV>(a, b, nl, p.n, ls, Ns, tw); Ns *= 3; }
+    const int R = p.radix[s];
+    switch (R) {
+      case 4: fft_stage<4, INV>(a, b, nl, p.n, ls, Ns, tw); break;
+      case 2: fft_stage<2, INV>(a, b, nl, p.n, ls, Ns, tw); break;
+      case 3: fft_stage<3, INV>(a, b, nl, p.n, ls, Ns, tw); break;
+      default:
+        if constexpr (ANY) {
+          if (R == 5) fft_stage<5, INV>(a, b, nl, p.n, ls, Ns, tw);
+          else if (R == 7) fft_stage<7, INV>(a, b, nl, p.n, ls, Ns, tw);
+          else fft_stage_generic<INV>(a, b, nl, p.n, ls, Ns, R, tw);
+        }
+        break;
+    }
+    Ns *= R;
     __syncthreads();
     float2* t = a;
     a = b;
@@ -159,6 +249,7 @@ KAIR_DEV float row_src(const RowSrc& s, int plane, int y, int v, int H, int W) {
   }
 }
 
+template <bool ANY>
 __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(RowSrc src, float2* __restrict__ T, int H, int W, int R,
                                                            FftPlan pw) {
   extern __shared__ float2 sm[];
@@ -174,7 +265,7 @@ __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(RowSrc src, float2* _
     a[r * ls + v] = make_float2(row_src(src, plane, y0 + r, v, H, W), 0.f);
   }
   __syncthreads();
-  const float2* res = fft_lines<false>(a, b, R, ls, pw, tw);
+  const float2* res = fft_lines<false, ANY>(a, b, R, ls, pw, tw);
   for (int i = threadIdx.x; i < R * W; i += blockDim.x) {
     const int v = fdiv(i, dR), r = i - v * R;
     T[((long)plane * W + v) * H + y0 + r] = res[r * ls + v];
@@ -197,6 +288,7 @@ struct ColArgs {
   int C, H, W, sf;
 };
 
+template <bool ANY>
 __global__ __launch_bounds__(256) void fft_cols_kernel(ColArgs A, int mode, FftPlan ph) {
   extern __shared__ float2 sm[];
   __shared__ float red[4];
@@ -213,7 +305,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(ColArgs A, int mode, FftP
     a[q * ls + u] = A.T[((long)plane * A.W + g + q * Wg) * H + u];
   }
   __syncthreads();
-  float2* F = fft_lines<false>(a, b, sf, ls, ph, tw);
+  float2* F = fft_lines<false, ANY>(a, b, sf, ls, ph, tw);
   float2* S = (F == a) ? b : a;
   const float inv_n = 1.0f / (float)(sf * sf);
   auto lidx = [&](int q, int u) { return ((long)plane * A.W + g + q * Wg) * H + u; };
@@ -298,7 +390,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(ColArgs A, int mode, FftP
     if (!A.Tout) return;
   }
   __syncthreads();
-  const float2* res = fft_lines<true>(F, S, sf, ls, ph, tw);
+  const float2* res = fft_lines<true, ANY>(F, S, sf, ls, ph, tw);
   for (int i = threadIdx.x; i < sf * H; i += blockDim.x) {
     const int q = fdiv(i, dH), u = i - q * H;
     A.Tout[lidx(q, u)] = res[q * ls + u];
@@ -308,7 +400,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(ColArgs A, int mode, FftP
 // ------------------------------------------------------------------------------------------
 // pass 3: rows, inverse, transposed complex -> real
 // ------------------------------------------------------------------------------------------
-template <typename TO>
+template <typename TO, bool ANY>
 __global__ __launch_bounds__(256) void fft_rows_inv_kernel(const float2* __restrict__ T, TO* __restrict__ dst, int nhwc,
                                                            int C, long ld, float scale, int H, int W, int R, FftPlan pw) {
   extern __shared__ float2 sm[];
@@ -324,7 +416,7 @@ __global__ __launch_bounds__(256) void fft_rows_inv_kernel(const float2* __restr
     a[r * ls + v] = T[((long)plane * W + v) * H + y0 + r];
   }
   __syncthreads();
-  const float2* res = fft_lines<true>(a, b, R, ls, pw, tw);
+  const float2* res = fft_lines<true, ANY>(a, b, R, ls, pw, tw);
   const int bb = plane / C, c = plane - bb * C;
   for (int i = threadIdx.x; i < R * W; i += blockDim.x) {
     const int r = fdiv(i, dW), v = i - r * W;
@@ -544,16 +636,28 @@ __global__ __launch_bounds__(256) void usr_pad_kernel(const T* __restrict__ src,
 }
 
 int make_plan(int n, FftPlan* p) {
+  if (n < 2 || n > 2048) return kair_set_error(KAIR_ERR_ARG, "usr fft: length %d is outside [2, 2048]", n);
+  *p = FftPlan{};
   p->n = n;
-  p->nst = 0;
-  p->enc = 0;
   int m = n;
-  auto push = [&](int code) { p->enc |= code << (2 * p->nst); ++p->nst; };
-  while (m % 4 == 0 && p->nst < 15) { push(2); m /= 4; }
-  while (m % 2 == 0 && p->nst < 15) { push(0); m /= 2; }
-  while (m % 3 == 0 && p->nst < 15) { push(1); m /= 3; }
-  if (m != 1) return kair_set_error(KAIR_ERR_ARG, "usr fft: length %d is not 2^a 3^b (<= 2048)", n);
+  auto take = [&](int r) {
+    while (m % r == 0) { p->radix[p->nst++] = (unsigned short)r; m /= r; }
+  };
+  // 4s, 2s, 3s (the stage order lengths 2^a 3^b have always had), 5s, 7s, then the other primes ascending
+  take(4);
+  take(2);
+  take(3);
+  take(5);
+  take(7);
+  for (int r = 11; m > 1; r += 2) take(r);
   return 0;
+}
+
+// a plan the radix-4/2/3 instantiation of the kernels runs
+bool plan_is_234(const FftPlan& p) {
+  for (int s = 0; s < p.nst; ++s)
+    if (p.radix[s] > 4) return false;
+  return true;
 }
 
 int row_block(int H, int W) {
@@ -581,8 +685,12 @@ extern "C" int kair_usr_fft_rows(const float* src, int src_mode, int C, long ld,
   const int R = row_block(H, W);
   RowSrc s{src, src_mode, C > 0 ? C : 1, ld, kh, kw, sf};
   const size_t lds = (size_t)(W + 2 * R * (W + 1)) * sizeof(float2);
-  KAIR_LAUNCH(fft_rows_fwd_kernel, dim3(H / R, planes), dim3(256), lds, (hipStream_t)stream, s, (float2*)T, H, W, R,
-                     pw);
+  if (plan_is_234(pw))
+    KAIR_LAUNCH(fft_rows_fwd_kernel<false>, dim3(H / R, planes), dim3(256), lds, (hipStream_t)stream, s, (float2*)T, H,
+                       W, R, pw);
+  else
+    KAIR_LAUNCH(fft_rows_fwd_kernel<true>, dim3(H / R, planes), dim3(256), lds, (hipStream_t)stream, s, (float2*)T, H,
+                       W, R, pw);
   KAIR_CHECK_LAUNCH();
   return 0;
 }
@@ -603,7 +711,10 @@ extern "C" int kair_usr_fft_cols(int mode, const void* T, void* T_out, const voi
             alpha_stride, part, C, H, W, sf};
   const size_t lds = (size_t)(H + 2 * sf * (H + 1)) * sizeof(float2);
   KAIR_CHECK_ARG(lds <= 150 * 1024, "usr_fft_cols: sf %d x H %d lines exceed LDS", sf, H);
-  KAIR_LAUNCH(fft_cols_kernel, dim3(W / sf, planes), dim3(256), lds, (hipStream_t)stream, a, mode, ph);
+  if (plan_is_234(ph))
+    KAIR_LAUNCH(fft_cols_kernel<false>, dim3(W / sf, planes), dim3(256), lds, (hipStream_t)stream, a, mode, ph);
+  else
+    KAIR_LAUNCH(fft_cols_kernel<true>, dim3(W / sf, planes), dim3(256), lds, (hipStream_t)stream, a, mode, ph);
   KAIR_CHECK_LAUNCH();
   return 0;
 }
@@ -619,12 +730,22 @@ extern "C" int kair_usr_ifft_rows(const void* T, void* dst, int nhwc, int dst_dt
   const size_t lds = (size_t)(W + 2 * R * (W + 1)) * sizeof(float2);
   hipStream_t s = (hipStream_t)stream;
   const int Cc = C > 0 ? C : 1;
-  if (dst_dtype == KAIR_BF16)
-    KAIR_LAUNCH(fft_rows_inv_kernel<bf16>, dim3(H / R, planes), dim3(256), lds, s, (const float2*)T, (bf16*)dst, nhwc,
-                       Cc, ld, scale, H, W, R, pw);
-  else
-    KAIR_LAUNCH(fft_rows_inv_kernel<float>, dim3(H / R, planes), dim3(256), lds, s, (const float2*)T, (float*)dst,
-                       nhwc, Cc, ld, scale, H, W, R, pw);
+  const bool any = !plan_is_234(pw);
+  if (dst_dtype == KAIR_BF16) {
+    if (any)
+      KAIR_LAUNCH((fft_rows_inv_kernel<bf16, true>), dim3(H / R, planes), dim3(256), lds, s, (const float2*)T,
+                         (bf16*)dst, nhwc, Cc, ld, scale, H, W, R, pw);
+    else
+      KAIR_LAUNCH((fft_rows_inv_kernel<bf16, false>), dim3(H / R, planes), dim3(256), lds, s, (const float2*)T,
+                         (bf16*)dst, nhwc, Cc, ld, scale, H, W, R, pw);
+  } else {
+    if (any)
+      KAIR_LAUNCH((fft_rows_inv_kernel<float, true>), dim3(H / R, planes), dim3(256), lds, s, (const float2*)T,
+                         (float*)dst, nhwc, Cc, ld, scale, H, W, R, pw);
+    else
+      KAIR_LAUNCH((fft_rows_inv_kernel<float, false>), dim3(H / R, planes), dim3(256), lds, s, (const float2*)T,
+                         (float*)dst, nhwc, Cc, ld, scale, H, W, R, pw);
+  }
   KAIR_CHECK_LAUNCH();
   return 0;
 }

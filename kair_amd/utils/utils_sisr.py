@@ -5,6 +5,15 @@ gen_kernel: the anisotropic Gaussian blur kernel of utils_sisr.py:172-215, resta
 degrade:    the classical degradation  L = (k (*) H, circular)[0::sf, 0::sf] + sigma N  of whole images on the
             device (kair_usr_degrade), the forward model USRNet's data step (p2o centring) assumes.
 wrap_blur:  the same blur on the host (float64 torch conv2d over a wrapped pad), for the file-based dataset.
+
+The closed-form data step of plug-and-play restoration (DPIR, kair_amd/main_dpir.py), for that forward model:
+p2o, upsample, pre_calculate, data_solution: the reference's functions as plain torch.fft, in the dtype and on the
+            device of their arguments -- the host path and the tests' float64 reference.  The reference file was not
+            available when they were written; they restate network_usrnet_v1.py's p2o / upsample / DataNet.forward,
+            which the reference's utils_sisr.py shares.
+HostDataStep / DataStep: the data step of one (y, k, sf) as an object with solve(x, alpha): torch.fft, and the
+            three-launch HIP path (csrc/fft.hip) with FB, the alias mean of |FB|^2 and conj(FB) F(y up) resident in
+            the kernels' transposed layout.
 """
 import math
 import random
@@ -80,3 +89,137 @@ def degrade(H, k, sf, sigma=0, trunc8=False, seed=0, step=0):
     L = torch.empty(N, C, -(-Hs // sf), -(-Ws // sf), device=H.device)
     _hip.usr_degrade(H, k, int(sf), sig, trunc8, seed, step, L)
     return L
+
+
+# ------------------------------------------------------------------------------------------
+# the closed-form data step  argmin_z ||(k (*) z)[::sf, ::sf] - y||^2 + alpha ||z - x||^2
+# ------------------------------------------------------------------------------------------
+FFT_MAX_LEN = 2048            # csrc/fft.hip: a line DFT is LDS-resident
+FFT_MAX_LDS = 150 * 1024      # kair_usr_fft_cols: sf column lines, two buffers and the twiddle table
+
+
+def splits(a, sf):
+    """[..., H, W] -> [..., H / sf, W / sf, sf * sf]: the sf x sf blocks of a spectrum that alias onto one
+    frequency of the sf-fold downsampled grid."""
+    b = torch.stack(torch.chunk(a, sf, dim=-2), dim=-1)
+    return torch.cat(torch.chunk(b, sf, dim=-2), dim=-1)
+
+
+def p2o(psf, shape):
+    """PSF [..., kh, kw] -> OTF [..., H, W]: zero-pad to shape, roll the centre tap (kh // 2, kw // 2) to the
+    origin, fft2."""
+    kh, kw = psf.shape[-2:]
+    otf = psf.new_zeros(psf.shape[:-2] + tuple(shape))
+    otf[..., :kh, :kw] = psf
+    otf = torch.roll(otf, (-(kh // 2), -(kw // 2)), dims=(-2, -1))
+    return torch.fft.fft2(otf)
+
+
+def upsample(x, sf=3):
+    """Zero-filling upsampler: x at [..., ::sf, ::sf] of an sf-fold larger grid."""
+    z = x.new_zeros(x.shape[:-2] + (x.shape[-2] * sf, x.shape[-1] * sf))
+    z[..., ::sf, ::sf] = x
+    return z
+
+
+def pre_calculate(y, k, sf):
+    """(FB, FBC, F2B, FBFy) of LQ images y [B, C, h, w] and kernels k [B or 1, 1, kh, kw] (or [kh, kw]):
+    FB = p2o(k) on the HR grid, its conjugate, |FB|^2, and conj(FB) fft2(upsample(y, sf))."""
+    if k.dim() == 2:
+        k = k[None, None]
+    h, w = y.shape[-2:]
+    FB = p2o(k.to(y.dtype), (h * sf, w * sf))
+    FBC = torch.conj(FB)
+    F2B = torch.abs(FB) ** 2
+    FBFy = FBC * torch.fft.fft2(upsample(y, sf))
+    return FB, FBC, F2B, FBFy
+
+
+def data_solution(x, FB, FBC, F2B, FBFy, alpha, sf):
+    """The minimiser of ||(k (*) z)[::sf, ::sf] - y||^2 + alpha ||z - x||^2 (circular blur), in closed form.
+    alpha: a number or a tensor broadcastable against x ([B, 1, 1, 1])."""
+    FR = FBFy + torch.fft.fft2(alpha * x)
+    FBR = torch.mean(splits(FB * FR, sf), dim=-1)
+    invW = torch.mean(splits(F2B, sf), dim=-1)
+    invWBR = FBR / (invW + alpha)
+    FX = (FR - FBC * invWBR.repeat(1, 1, sf, sf)) / alpha
+    return torch.real(torch.fft.ifft2(FX))
+
+
+def _alpha_of(alpha, B, device, dtype):
+    """alpha (a number, a one-element tensor or [B]) as a tensor of 1 or B elements on `device`; no host read."""
+    if torch.is_tensor(alpha):
+        al = alpha.to(device=device, dtype=dtype).reshape(-1)
+        if al.numel() not in (1, B):
+            raise ValueError(f"data step: alpha has {al.numel()} elements for a batch of {B}")
+        return al
+    return torch.full((1,), float(alpha), device=device, dtype=dtype)
+
+
+class HostDataStep:
+    """solve(x, alpha) = data_solution(x, ..., alpha, sf) for one (y, k, sf), in y's dtype on y's device."""
+
+    def __init__(self, y, k, sf=1):
+        self.sf = int(sf)
+        self.B = y.shape[0]
+        self.pre = pre_calculate(y, k.to(y.device), self.sf)
+
+    def solve(self, x, alpha):
+        al = _alpha_of(alpha, self.B, x.device, x.dtype).reshape(-1, 1, 1, 1)
+        return data_solution(x, *self.pre, al, self.sf)
+
+
+class DataStep:
+    """The data step on the device: FB, invW = mean(splits(|FB|^2, sf)) and FBFy are built once by the rows / cols
+    passes of csrc/fft.hip and stay in the kernels' transposed float2 layout; solve(x, alpha) is three launches
+    (rows DFT, columns DFT + closed form + inverse columns DFT, inverse rows DFT) and no host synchronisation.
+
+    y: [B, C, h, w] device tensor; k: [B, 1, kh, kw], or one [1, 1, kh, kw] / [kh, kw] kernel for all images;
+    alpha of solve: a number or a tensor of 1 or B elements.  The HR grid h sf x w sf may have any side lengths in
+    [2, 2048]; sf whole column lines have to fit the 150 KB of LDS the columns pass uses."""
+
+    def __init__(self, y, k, sf=1):
+        from .. import _hip
+        if y.dim() != 4 or not y.is_cuda:
+            raise ValueError("DataStep: y must be a device tensor [B, C, h, w]")
+        sf = int(sf)
+        B, C, h, w = y.shape
+        Hh, Ww = h * sf, w * sf
+        if sf < 1 or not (2 <= Hh <= FFT_MAX_LEN and 2 <= Ww <= FFT_MAX_LEN):
+            raise ValueError(f"DataStep: the HR grid {Hh} x {Ww} is outside the line-DFT range [2, {FFT_MAX_LEN}]")
+        lds = (Hh + 2 * sf * (Hh + 1)) * 8
+        if lds > FFT_MAX_LDS:
+            raise ValueError(f"DataStep: sf {sf} column lines of {Hh} need {lds} bytes of LDS (limit {FFT_MAX_LDS})")
+        if k.dim() == 2:
+            k = k[None, None]
+        if k.dim() != 4 or k.shape[1] != 1 or k.shape[0] not in (1, B):
+            raise ValueError(f"DataStep: k {tuple(k.shape)} is neither [B, 1, kh, kw] nor one kernel")
+        kh, kw = k.shape[-2:]
+        if kh > Hh or kw > Ww:
+            raise ValueError(f"DataStep: the {kh} x {kw} kernel is larger than the {Hh} x {Ww} grid")
+        dev = y.device
+        k = k.to(dev, torch.float32).expand(B, 1, kh, kw).contiguous()
+        y = y.float().contiguous()
+        self.shape, self.sf = (B, C, Hh, Ww), sf
+        self.FB = torch.empty(B * Hh * Ww * 2, device=dev)
+        self.invW = torch.empty(B * (Hh // sf) * (Ww // sf), device=dev)
+        self.FBFy = torch.empty(B * C * Hh * Ww * 2, device=dev)
+        self.T = torch.empty_like(self.FBFy)
+        _hip.usr_fft_rows(k, _hip.USR_SRC_PSF, 1, 0, kh, kw, 1, self.FB, B, Hh, Ww)
+        _hip.usr_fft_cols(_hip.USR_COL_FB, self.FB, self.FB, None, None, None, self.invW, None, 0, None, B, 1, Hh, Ww, sf)
+        _hip.usr_fft_rows(y, _hip.USR_SRC_ZUP, C, 0, 0, 0, sf, self.FBFy, B * C, Hh, Ww)
+        _hip.usr_fft_cols(_hip.USR_COL_FBFY, self.FBFy, self.FBFy, self.FB, None, None, self.invW, None, 0, None, B * C,
+                          C, Hh, Ww, sf)
+
+    def solve(self, x, alpha):
+        from .. import _hip
+        B, C, Hh, Ww = self.shape
+        if tuple(x.shape) != self.shape or x.device != self.FB.device:
+            raise ValueError(f"DataStep.solve: x {tuple(x.shape)} on {x.device}, expected {self.shape} on {self.FB.device}")
+        al = _alpha_of(alpha, B, x.device, torch.float32)
+        z = torch.empty(B, C, Hh, Ww, device=x.device)
+        _hip.usr_fft_rows(x.float().contiguous(), _hip.USR_SRC_NCHW, C, 0, 0, 0, 1, self.T, B * C, Hh, Ww)
+        _hip.usr_fft_cols(_hip.USR_COL_DATA_FWD, self.T, self.T, self.FB, self.FBFy, None, self.invW, al,
+                          int(al.numel() > 1), None, B * C, C, Hh, Ww, self.sf)
+        _hip.usr_ifft_rows(self.T, z, False, C, 0, 1.0 / (Hh * Ww), B * C, Hh, Ww)
+        return z
