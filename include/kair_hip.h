@@ -853,6 +853,31 @@ int kair_usr_degrade(const float* x, int N, int C, int Hs, int Ws, int sf, const
                      const float* sigma, int sstride, int trunc8, unsigned long long seed, unsigned long long step,
                      float* outL, int direct, void* stream);
 
+/* ---- SRMD training data (csrc/synth_srmd.hip; DatasetSRMD.__getitem__, data/dataset_srmd.py) -------------------
+ * kair_srmd_kernels: B blur kernels out_k [B][15][15] fp32 and their codes out_code [B][ncode] in one launch.  Sample b
+ * reads kpar[b * kstride + {0, 1, 2}] = {theta, l1, l2}: k[y][x] = exp(-z^T Sigma^-1 z / 2) / sum, z = (x - 7, y - 7),
+ * Sigma = R diag(l1, l2) R^T, R = [[cos, -sin], [sin, cos]](theta) (utils_sisr.anisotropic_gaussian; evaluated in
+ * fp64, l1 and l2 clamped to >= 1e-6).  code[i] = sum_f P[i][f] k[f % 15][f / 15] (P [ncode][225] fp32, the kernel
+ * flattened column-major), one fp32 fmaf chain in f order per code: repeated calls are bit-identical.
+ *
+ * kair_synth_srmd: params rows of pstride >= 5 ints {image, rnd_h, rnd_w, mode, ...} (rnd_* in H coordinates, values
+ * clamped into the pool), the sample's noise level sigma_b (already / 255) as float32 bits in column scol >= 4.
+ * outH [B][C][PS][PS] = the augmented crops.  outL [B][C + ncode + noise_ch][PS/sf][PS/sf]: channels < C are
+ *   Bl[y][x] = sum_{u, v} k[b][u][v] H[(y + 7 - u) mod PS][(x + 7 - v) mod PS]       (circular 15 x 15 blur, fp32)
+ *   L = Mh Bl Mw^T + sigma_b N(0, 1)
+ * with Mh = Mw the MATLAB-bicubic resize of a PS-pixel axis by 1 / sf given as taps wt / it [PS/sf][P] (weights and
+ * reflected source indices, utils_image.bicubic_taps; rows first, then columns, fmaf chains in tap order) and the Philox
+ * normals of kair_synth_dn keyed by (seed, step) and the element's index in the [B][C][PS/sf][PS/sf] block; sigma_b = 0
+ * adds nothing.  Channels C .. C + ncode - 1 are the constants code[b][i] (code [B][ncode]), channel C + ncode (with
+ * noise_ch 1) is the constant sigma_b.  One launch; the blurred patch stays in LDS.  A patch whose single-L-row band
+ * does not fit in 150 KB of LDS is an argument error. */
+int kair_srmd_kernels(const float* kpar, int kstride, const float* P, int ncode, int B, float* out_k, float* out_code,
+                      void* stream);
+int kair_synth_srmd(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
+                    int PS, int sf, const float* k, const float* code, int ncode, int noise_ch, const float* wt,
+                    const int* it, int P, unsigned long long seed, unsigned long long step, float* outH, float* outL,
+                    void* stream);
+
 /* ---- JPEG CAR training data (csrc/synth_jpeg.hip; DatasetJPEG.__getitem__, data/dataset_jpeg.py:40-96) ----------
  * The lossy part of a baseline JPEG encode + decode in libjpeg's 32-bit integer arithmetic (jfdctint / jidctint,
  * Annex-K tables scaled by the quality, force_baseline), bit-equal to the decoder's pixels; the entropy coding, which

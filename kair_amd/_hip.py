@@ -237,6 +237,9 @@ _SIGS = {
                        c_int, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_int, c_vp],
     "kair_usr_degrade": [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_long, c_int, c_int, c_vp, c_int, c_int,
                          ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_int, c_vp],
+    "kair_srmd_kernels": [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
+    "kair_synth_srmd": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int,
+                        c_vp, c_vp, c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_vp],
     "kair_jpeg_workspace_bytes": [c_int, c_int, c_int, c_int],
     "kair_jpeg_roundtrip": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp],
     "kair_rgb2gray8": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],
@@ -1220,6 +1223,46 @@ def usr_degrade(x, k, sf, sigma, trunc8, seed, step, outL, direct=False):
     kstride = 0 if k.numel() == kh * kw else kh * kw
     check(lib().kair_usr_degrade(ptr(x), N, C, Hs, Ws, sf, ptr(k), kstride, kh, kw, sp, ss, int(trunc8), seed, step,
                                  ptr(outL), int(direct), stream_ptr()), "usr_degrade")
+
+
+def srmd_kernels(kpar, P, out_k, out_code):
+    """out_k [B, 1, 15, 15] and out_code [B, ncode] <- the anisotropic Gaussian kernels of kpar [B, >= 3] fp32 {theta,
+    l1, l2} and their codes P @ vec_F(k), P [ncode, 225] fp32 (kair_srmd_kernels)."""
+    require_device(kpar, P, out_k, out_code)
+    B = out_k.shape[0]
+    _fp32(out_k, (B, 1, 15, 15), "srmd_kernels: out_k")
+    if P.dtype != torch.float32 or not P.is_contiguous() or P.dim() != 2 or P.shape[1] != 225:
+        raise ValueError("srmd_kernels: P must be a contiguous fp32 [ncode, 225]")
+    _fp32(out_code, (B, P.shape[0]), "srmd_kernels: out_code")
+    if kpar.shape[0] < B:
+        raise ValueError("srmd_kernels: fewer parameter rows than kernels")
+    kp, ks = _rows_of(kpar, torch.float32, 3, "srmd_kernels kpar")
+    check(lib().kair_srmd_kernels(kp, ks, ptr(P), P.shape[0], B, ptr(out_k), ptr(out_code), stream_ptr()), "srmd_kernels")
+
+
+def synth_srmd(pool, params, B, PS, sf, k, code, noise_channel, taps, seed, step, outH, outL, sigma_col=4):
+    """SRMD batch (kair_synth_srmd): params [B, >= 5] int32 {image, rnd_h, rnd_w, mode} plus the float32 bits of the
+    sample's sigma / 255 in column sigma_col; k [B, 1, 15, 15]; code [B, ncode]; taps = (indices int32, weights fp32)
+    [PS // sf, P] of utils_image.bicubic_taps(PS, PS // sf, 1 / sf); outH [B, C, PS, PS], outL [B, C + ncode (+ 1 with
+    noise_channel), PS // sf, PS // sf]."""
+    require_device(pool, params, k, code, outH, outL, *taps)
+    N, C, Hs, Ws = _images(pool, "synth_srmd: pool")
+    if PS < 1 or sf < 1 or PS % sf:
+        raise ValueError(f"synth_srmd: the patch size {PS} is not divisible by the scale {sf}")
+    LS = PS // sf
+    _fp32(k, (B, 1, 15, 15), "synth_srmd: k")
+    if code.dtype != torch.float32 or not code.is_contiguous() or code.dim() != 2 or code.shape[0] != B:
+        raise ValueError("synth_srmd: code must be a contiguous fp32 [B, ncode]")
+    it, wt = taps
+    if (it.dtype != torch.int32 or wt.dtype != torch.float32 or it.dim() != 2 or it.shape[0] != LS or
+            wt.shape != it.shape or not it.is_contiguous() or not wt.is_contiguous()):
+        raise ValueError(f"synth_srmd: taps must be contiguous (int32, fp32) [{LS}, P]")
+    _fp32(outH, (B, C, PS, PS), "synth_srmd: output")
+    _fp32(outL, (B, C + code.shape[1] + int(bool(noise_channel)), LS, LS), "synth_srmd: output")
+    pp, ps = _sample_rows(params, B, max(5, sigma_col + 1), "synth_srmd params")
+    check(lib().kair_synth_srmd(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, sf, ptr(k), ptr(code), code.shape[1],
+                                int(bool(noise_channel)), ptr(wt), ptr(it), it.shape[1], seed, step, ptr(outH), ptr(outL),
+                                stream_ptr()), "synth_srmd")
 
 
 def jpeg_roundtrip(x, quality, out):

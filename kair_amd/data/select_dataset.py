@@ -4,7 +4,8 @@ plus its noise-level map, train_fdncnn.json and train_drunet.json), 'ffdnet' (Da
 noise level as a second input "C"), 'sr' (DatasetSR, configs 2/4/5),
 'usrnet' (DatasetUSRNet, config 3), 'jpeg' (DatasetJPEG, the JPEG artifact-reduction SwinIR of
 train_swinir_car_jpeg.json) and 'blindsr' (DatasetBlindSR, the BSRGAN degradation of
-train_bsrgan_x4_psnr.json and train_swinir_sr_realworld_x4_psnr.json).
+train_bsrgan_x4_psnr.json and train_swinir_sr_realworld_x4_psnr.json) and 'srmd' (DatasetSRMD: the degraded LR image
+followed by its degradation map, train_srmd.json).
 Other dataset types are off the path and raise NotImplementedError naming the type."""
 
 
@@ -24,6 +25,9 @@ def define_Dataset(dataset_opt):
         from .dataset_jpeg import DatasetJPEG as D
     elif t in ("blindsr", "bsrnet", "bsrgan"):
         from .dataset_blindsr import DatasetBlindSR as D
+    elif t == "srmd":
+        from .dataset_srmd import DatasetSRMD as D
     else:
-        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, fdncnn, drunet, ffdnet, sr, usrnet, jpeg, blindsr).")
+        raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, fdncnn, drunet, ffdnet, sr, usrnet, jpeg, "
+                                  "blindsr, srmd).")
     return D(dataset_opt)

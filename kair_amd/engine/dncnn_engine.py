@@ -1,4 +1,4 @@
-"""DnCNN / FDnCNN / FFDNet step program for MI355X.
+"""DnCNN / FDnCNN / FFDNet / SRMD step program for MI355X.
 
 Reference: /root/reference/models/network_dncnn.py:40-71 (DnCNN, out = x - model(x)), 128-149
 (FDnCNN, out = model(x)); layers from basicblock.conv (basicblock.py:61-98).  SURVEY §8 row a14.
@@ -11,7 +11,8 @@ activation gate and the two per-channel reductions; conv input / weight / bias g
 other conv programs.
 
 FFDNetEngine (below) runs the same layer loop over the half grid behind a PixelUnshuffle head (kair_ffd_pack) and a
-PixelShuffle store; DnCNNEngine keeps what differs in the six methods after convs().
+PixelShuffle store; SRMDEngine runs it on the LR grid with a last conv of up to 48 columns behind a PixelShuffle(2 / 3 / 4)
+store.  DnCNNEngine keeps what differs in the methods after convs().
 """
 import torch
 import torch.nn as nn
@@ -26,7 +27,7 @@ class DnCNNEngine(ConvEngineBase):
     def __init__(self, net, compute_dtype="bf16", residual=True):
         super().__init__(net, compute_dtype)
         self.residual = residual
-        mods = list(net.model)
+        mods = self._conv_modules(net)
         self.device = mods[0].weight.device
         layers, i = [], 0
         while i < len(mods):
@@ -46,19 +47,30 @@ class DnCNNEngine(ConvEngineBase):
         self.in_ch = layers[0][0].in_channels
         self.out_ch = layers[-1][0].out_channels
         self.nc = layers[0][0].out_channels
-        if self.nc % 8 or self.out_ch > 16:
+        if self.nc % 8:
             raise NotImplementedError("kair_amd DnCNN: nc multiple of 8, out_nc <= 16")
+        self.Cout_p = self._out_width()
         self.Cin_p = _rup(self.in_ch, 8)
         self.layers = []
         for li, (conv, bn, act, slope) in enumerate(layers):
-            cop = 16 if li == len(layers) - 1 else conv.out_channels
+            cop = self.Cout_p if li == len(layers) - 1 else conv.out_channels
             cip = self.Cin_p if li == 0 else conv.in_channels
             self.layers.append((_Conv(self, conv, cop, cip, need_dgrad=li > 0), bn, act, slope))
 
     def convs(self):
         return [c for c, _, _, _ in self.layers]
 
-    # ---- what a network with another head / tail overrides (FFDNetEngine) ----------------------
+    # ---- what a network with another head / tail overrides (FFDNetEngine, SRMDEngine) ----------
+    def _conv_modules(self, net):
+        """The modules of the conv stack, in order."""
+        return list(net.model)
+
+    def _out_width(self):
+        """The padded width of the last conv's output rows (and of the gradient rows P['dEf'] / P['dn'])."""
+        if self.out_ch > 16:
+            raise NotImplementedError("kair_amd DnCNN: nc multiple of 8, out_nc <= 16")
+        return 16
+
     def _grid(self, key):
         """The conv grid (rows, columns) of the plan keyed (B, h, w): the image itself."""
         return key[1], key[2]
@@ -74,11 +86,11 @@ class DnCNNEngine(ConvEngineBase):
         return H.epilogue(P["E"], mode=H.OUT_NCHW, ldo=0, bias=c.bp, img=(None, 1.0, self.out_ch, P["H"], P["W"]))
 
     def _loss(self, P, H_img, loss_weight, charb_eps, loss_type=None):
-        self.pixel_loss(P, P["E"], H_img, P["dEf"], 16, loss_weight, self.out_ch, P["H"], P["W"], charb_eps=charb_eps,
-                        loss_type=loss_type)
+        self.pixel_loss(P, P["E"], H_img, P["dEf"], self.Cout_p, loss_weight, self.out_ch, P["H"], P["W"],
+                        charb_eps=charb_eps, loss_type=loss_type)
 
     def _pack_grad(self, P, gE):
-        H.image_to_nhwc(gE.contiguous(), P["dEf"], 16, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])
+        H.image_to_nhwc(gE.contiguous(), P["dEf"], self.Cout_p, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])
 
     def _build_plan(self, key, infer):
         B = key[0]
@@ -93,8 +105,8 @@ class DnCNNEngine(ConvEngineBase):
         P["mean"] = [e(nc) if bn is not None else None for _, bn, _, _ in self.layers[:n_mid]]
         P["rstd"] = [e(nc) if bn is not None else None for _, bn, _, _ in self.layers[:n_mid]]
         P["E"] = self._out_image(P, key)
-        P["dEf"] = torch.zeros(M, 16, device=self.device)
-        P["dn"] = e(M, 16, dt=T)
+        P["dEf"] = torch.zeros(M, self.Cout_p, device=self.device)
+        P["dn"] = e(M, self.Cout_p, dt=T)
         P["G"], P["dz"] = e(M, nc), e(M, nc, dt=T)
         P["dzf"] = e(M, nc)   # fp32 gradient rows before the compute-dtype cast (bias gradients)
         P["bn_ws"] = e(H.bn_ws(nc))
@@ -149,14 +161,14 @@ class DnCNNEngine(ConvEngineBase):
         self.backward(grads, P)
 
     def backward(self, grads, P):
-        cd, nc = self.cd, self.nc
+        cd, nc, Co = self.cd, self.nc, self.Cout_p
         Hh, Ww, M = P["H"], P["W"], P["M"]
         # d model(x) = -dE for DnCNN (out = x - model(x)), dE for FDnCNN
-        H.act_grad_cast(P["dEf"], 16, None, 0, P["dn"], 16, M, 16, 0, 0.0, -1.0 if self.residual else 1.0)
+        H.act_grad_cast(P["dEf"], Co, None, 0, P["dn"], Co, M, Co, 0, 0.0, -1.0 if self.residual else 1.0)
         c = self.layers[-1][0]
         G = P["G"]
-        self._nt(H.im2col(P["dn"], Hh, Ww, 16, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * 16)
-        self.conv_wgrad(P, c, P["dn"], 16, H.im2col(P["a"][-1], Hh, Ww, nc), M, grads)
+        self._nt(H.im2col(P["dn"], Hh, Ww, Co, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * Co)
+        self.conv_wgrad(P, c, P["dn"], Co, H.im2col(P["a"][-1], Hh, Ww, nc), M, grads)
         for li in range(len(self.layers) - 2, -1, -1):
             c, bn, act, slope = self.layers[li]
             a, dz = P["a"][li], P["dz"]
@@ -228,3 +240,53 @@ class FFDNetEngine(DnCNNEngine):
 
     def _pack_grad(self, P, gE):
         H.ffd_pack(gE.contiguous(), None, P["dEf"], 16, P["B"], self.img_out, P["h"], P["w"])
+
+
+class SRMDEngine(DnCNNEngine):
+    """SRMD (network_srmd.SRMD): DnCNN's layer loop on the LR grid, no BatchNorm, no residual.
+
+    head: the LR image and its degradation-map channels arrive as one [B, in_nc, h, w] tensor; kair_image_to_nhwc packs
+          it into rows of _rup(in_nc, 8) channels (24 for 16..19), pad channels zero;
+    tail: the last conv has _rup(out_nc r^2, 16) output columns (16 / 32 / 48) and stores through KAIR_OUT_PSHUF_NCHW
+          (ps_r = r) straight into the [B, out_nc, r h, r w] image.  The HR-grid gradient reaches it as pre-shuffle rows
+          [M, Cop]: the fused pixel losses write them (ps_r = r, pad columns zero), an upstream autograd gradient goes
+          through pixel_unshuffle and kair_image_to_nhwc (outside any captured step).
+    Plans are keyed (B, h, w) of the LR input."""
+
+    def __init__(self, net, compute_dtype="bf16"):
+        self.r = int(net.upscale)
+        super().__init__(net, compute_dtype, residual=False)
+        if self.out_ch % (self.r * self.r):
+            raise NotImplementedError("kair_amd SRMD: the last conv writes out_nc * upscale^2 channels")
+        self.img_out = self.out_ch // (self.r * self.r)
+
+    def _conv_modules(self, net):
+        mods = list(net.model)
+        if not isinstance(mods[-1], nn.PixelShuffle) or mods[-1].upscale_factor != self.r:
+            raise NotImplementedError("kair_amd SRMD: the conv stack ends in PixelShuffle(upscale)")
+        return mods[:-1]
+
+    def _out_width(self):
+        if self.out_ch > 48:
+            raise NotImplementedError(f"kair_amd SRMD: out_nc * upscale^2 must be <= 48 (got {self.out_ch})")
+        return _rup(self.out_ch, 16)
+
+    def grad_segments(self):
+        """One gradient segment: 1.5 M parameters are one all-reduce bucket."""
+        return [list(self.net_ref().parameters())]
+
+    def _out_image(self, P, key):
+        B, h, w = key
+        return self._e(B, self.img_out, self.r * h, self.r * w)
+
+    def _out_epilogue(self, P, c):
+        return H.epilogue(P["E"], mode=H.OUT_PSHUF_NCHW, ldo=0, bias=c.bp, ps=(self.r, P["H"], P["W"]),
+                          img=(None, 1.0, self.img_out, P["H"], P["W"]))
+
+    def _loss(self, P, H_img, loss_weight, charb_eps, loss_type=None):
+        self.pixel_loss(P, P["E"], H_img, P["dEf"], self.Cout_p, loss_weight, self.img_out, self.r * P["H"],
+                        self.r * P["W"], ps_r=self.r, charb_eps=charb_eps, loss_type=loss_type)
+
+    def _pack_grad(self, P, gE):
+        rows = torch.nn.functional.pixel_unshuffle(gE.contiguous(), self.r).contiguous()   # [B, out_nc r^2, h, w]
+        H.image_to_nhwc(rows, P["dEf"], self.Cout_p, None, 1.0, P["B"], self.out_ch, P["H"], P["W"])

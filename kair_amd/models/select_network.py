@@ -2,8 +2,8 @@
 
 `opt['netG']['net_type']` selects the network; constructor kwargs are taken from opt['netG'] under
 the reference's key names, and init_weights() runs when opt['is_train'] (select_network.py:268-272).
-Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, rrdb, rrdbnet, usrnet, drunet.  Everything else the
-reference's define_G knows (srmd, dpsr, msrresnet*, imdn, vrt, rvrt, ...) is out of
+Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet.  Everything else the
+reference's define_G knows (dpsr, msrresnet*, imdn, vrt, rvrt, ...) is out of
 scope for this build and raises NotImplementedError naming the type.
 """
 import functools
@@ -13,7 +13,7 @@ from torch.nn import init
 
 logger = logging.getLogger("kair_amd")
 
-_ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "rrdb", "rrdbnet", "usrnet", "drunet")
+_ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "srmd", "rrdb", "rrdbnet", "usrnet", "drunet")
 
 
 def define_G(opt):
@@ -35,6 +35,10 @@ def define_G(opt):
     elif t == "ffdnet":   # two inputs: net(x, sigma), trained by ModelPlain2 ('plain2')
         from .network_ffdnet import FFDNet
         net = FFDNet(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], act_mode=o["act_mode"], **ek)
+    elif t == "srmd":   # one input: the LR image with its degradation-map channels, trained by ModelPlain ('plain')
+        from .network_srmd import SRMD
+        net = SRMD(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], upscale=o["scale"],
+                   act_mode=o["act_mode"], upsample_mode=o["upsample_mode"], **ek)
     elif t == "rrdb":
         from .network_rrdb import RRDB
         net = RRDB(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], gc=o["gc"], upscale=o["scale"],

@@ -14,6 +14,12 @@ p2o, upsample, pre_calculate, data_solution: the reference's functions as plain 
 HostDataStep / DataStep: the data step of one (y, k, sf) as an object with solve(x, alpha): torch.fft, and the
             three-launch HIP path (csrc/fft.hip) with FB, the alias mean of |FB|^2 and conj(FB) F(y up) resident in
             the kernels' transposed layout.
+
+The degradation of SRMD (network_srmd.py, data/dataset_srmd.py; the reference's utils_sisr.py restated from the
+published method), in the dtype and on the device of the arguments -- the host path and the tests' float64 side:
+anisotropic_gaussian, cal_pca_matrix, load_pca_matrix: the 15 x 15 kernel, and the PCA basis of its code;
+srmd_degradation_map: the kernel's code (and the noise level) stretched over the LR grid;
+srmd_degrade: circular blur, MATLAB-bicubic x1/sf, AWGN.  The device form is csrc/synth_srmd.hip.
 """
 import math
 import random
@@ -223,3 +229,125 @@ class DataStep:
                           int(al.numel() > 1), None, B * C, C, Hh, Ww, self.sf)
         _hip.usr_ifft_rows(self.T, z, False, C, 0, 1.0 / (Hh * Ww), B * C, Hh, Ww)
         return z
+
+
+# ------------------------------------------------------------------------------------------
+# SRMD: degradation maps  (kernel -> PCA code -> stretched map) and the degradation itself
+# ------------------------------------------------------------------------------------------
+SRMD_KSIZE, SRMD_DIM_PCA = 15, 15
+
+
+def anisotropic_gaussian(ksize=15, theta=0.0, l1=6.0, l2=6.0, dtype=torch.float64, device="cpu"):
+    """k(x) ~ exp(-x^T Sigma^-1 x / 2) on the integer grid centred at (ksize - 1) / 2, sum 1: [ksize, ksize], rows y,
+    columns x.  Sigma = R(theta) diag(l1, l2) R(theta)^T, R = [[cos, -sin], [sin, cos]]; l1, l2 are its eigenvalues
+    (variances, in pixels^2)."""
+    cs, sn = math.cos(theta), math.sin(theta)
+    a11 = cs * cs / l1 + sn * sn / l2
+    a12 = cs * sn * (1.0 / l1 - 1.0 / l2)
+    a22 = sn * sn / l1 + cs * cs / l2
+    ax = torch.arange(ksize, dtype=dtype, device=device) - (ksize - 1) / 2.0
+    zy, zx = torch.meshgrid(ax, ax, indexing="ij")
+    raw = torch.exp(-0.5 * (a11 * zx * zx + 2.0 * a12 * zx * zy + a22 * zy * zy))
+    return raw / raw.sum()
+
+
+def vec_f(k):
+    """[..., kh, kw] -> [..., kh kw], column-major (numpy's order='F'): element c kh + r is k[r][c]."""
+    return k.transpose(-1, -2).reshape(*k.shape[:-2], -1)
+
+
+def draw_srmd_kernel(rng, l_max=10.0):
+    """(theta, l1, l2) of one training kernel: theta ~ U(0, pi), l1 ~ U(0.1, l_max), l2 ~ U(0.1, l1), in that order
+    from rng (random.Random)."""
+    theta = rng.uniform(0.0, math.pi)
+    l1 = rng.uniform(0.1, l_max)
+    return theta, l1, rng.uniform(0.1, l1)
+
+
+_PCA_CACHE = {}
+
+
+def cal_pca_matrix(ksize=15, l_max=10.0, dim_pca=15, num_samples=500, seed=0):
+    """The PCA basis of the kernel codes, [dim_pca, ksize^2] float64: num_samples kernels drawn by draw_srmd_kernel
+    from random.Random(seed), flattened column-major into the columns of X [ksize^2, n]; the first dim_pca left
+    singular vectors of X X^T as rows (no mean subtraction).  Each row's sign is fixed so that its entry of largest
+    magnitude is positive; the result is the same for the same arguments."""
+    key = (ksize, float(l_max), dim_pca, num_samples, seed)
+    if key not in _PCA_CACHE:
+        rng = random.Random(seed)
+        X = torch.stack([vec_f(anisotropic_gaussian(ksize, *draw_srmd_kernel(rng, l_max))) for _ in range(num_samples)], 1)
+        U = torch.linalg.svd(X @ X.T)[0]
+        P = U[:, :dim_pca].T.contiguous()
+        lead = P.gather(1, P.abs().argmax(1, keepdim=True))
+        _PCA_CACHE[key] = P * torch.where(lead < 0, -1.0, 1.0)
+    return _PCA_CACHE[key].clone()
+
+
+def load_pca_matrix(path):
+    """A PCA basis [dim_pca, ksize^2] from a .npy or .pt file (e.g. `p` of the reference's srmd_pca_matlab.mat exported
+    with numpy.save), float64."""
+    if str(path).endswith(".npy"):
+        import numpy as np
+        P = torch.from_numpy(np.load(path))
+    elif str(path).endswith(".pt"):
+        P = torch.as_tensor(torch.load(path, map_location="cpu"))
+    else:
+        raise ValueError(f"load_pca_matrix: {path!r} is neither .npy nor .pt")
+    if P.dim() != 2:
+        raise ValueError(f"load_pca_matrix: expected a [dim_pca, ksize^2] matrix, got {tuple(P.shape)}")
+    return P.double().contiguous()
+
+
+def srmd_degradation_map(k, sigma, P, h, w, noise_channel=True):
+    """[B, dim_pca (+ 1), h, w]: the code P @ vec_F(k) of each kernel k [B, 1, ks, ks], followed by the noise level
+    sigma [B] when noise_channel, each constant over h x w.  In k's dtype, on k's device."""
+    B = k.shape[0]
+    P = torch.as_tensor(P).to(k)
+    if k.dim() != 4 or k.shape[1] != 1 or P.dim() != 2 or P.shape[1] != k.shape[-2] * k.shape[-1]:
+        raise ValueError(f"srmd_degradation_map: k {tuple(k.shape)} and P {tuple(P.shape)} do not fit")
+    code = vec_f(k[:, 0]) @ P.T
+    if noise_channel:
+        s = torch.as_tensor(sigma).to(k).reshape(-1)
+        if s.numel() != B:
+            raise ValueError(f"srmd_degradation_map: sigma holds {s.numel()} levels for {B} kernels")
+        code = torch.cat((code, s.view(B, 1)), 1)
+    return code.view(B, -1, 1, 1).expand(B, code.shape[1], h, w).contiguous()
+
+
+def wrap_blur_each(x, k):
+    """wrap_blur with one kernel per sample, in x's dtype: x [B, C, H, W], k [B, 1, kh, kw] (or [kh, kw] for all)."""
+    B, C, Hh, Ww = x.shape
+    k = k.to(x)
+    if k.dim() == 2:
+        k = k[None, None].expand(B, 1, *k.shape)
+    kh, kw = k.shape[-2:]
+    rows = torch.arange(-(kh - 1 - kh // 2), Hh + kh // 2, device=x.device) % Hh
+    cols = torch.arange(-(kw - 1 - kw // 2), Ww + kw // 2, device=x.device) % Ww
+    xp = x[..., rows, :][..., cols].reshape(1, B * C, rows.numel(), cols.numel())
+    wgt = k.flip(-1, -2).expand(B, C, kh, kw).reshape(B * C, 1, kh, kw)
+    return torch.nn.functional.conv2d(xp, wgt, groups=B * C).view(B, C, Hh, Ww)
+
+
+def srmd_degrade(x, k, sf, sigma=None, seed=0):
+    """SRMD's degradation of x [B, C, H, W] (or [C, H, W]), in x's dtype: the circular (wrap) blur with each sample's
+    kernel k [B, 1, ks, ks] (or one [ks, ks]), the MATLAB-bicubic utils_image.imresize by 1 / sf (antialiased; its
+    fp32 weights, applied in x's dtype), then AWGN of per-sample std sigma ([B] or a number, already divided by 255;
+    None or 0: none) from torch.Generator().manual_seed(seed)."""
+    lead = x.dim() == 3
+    x = x[None] if lead else x
+    B = x.shape[0]
+    y = wrap_blur_each(x, k)
+    if sf != 1:
+        Hh, Ww = y.shape[-2:]
+        Mh = util.resize_matrix(Hh, math.ceil(Hh / sf), 1.0 / sf, True, y.device).to(y.dtype)
+        Mw = util.resize_matrix(Ww, math.ceil(Ww / sf), 1.0 / sf, True, y.device).to(y.dtype)
+        y = torch.matmul(torch.matmul(Mh, y), Mw.T)
+    if sigma is not None:
+        s = torch.as_tensor(sigma, dtype=y.dtype).reshape(-1)
+        s = s.expand(B) if s.numel() == 1 else s
+        if s.numel() != B:
+            raise ValueError(f"srmd_degrade: sigma holds {s.numel()} levels for a batch of {B}")
+        if bool((s != 0).any()):
+            n = torch.randn(y.shape, generator=torch.Generator().manual_seed(seed), dtype=y.dtype)
+            y = y + s.view(B, 1, 1, 1).to(y.device) * n.to(y.device)
+    return y[0] if lead else y
