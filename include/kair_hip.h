@@ -650,6 +650,13 @@ int kair_act_grad_cast(const float* G, long ldg, const void* X, int x_dtype, lon
  * src fp32 [B, 2H, 2W] rows of stride lds; dst fp32 [B, H, W] rows of stride ldd. */
 int kair_sumpool2x(const float* src, long lds, float* dst, long ldd, int B, int H, int W, int C, int accumulate,
                    void* stream);
+/* kair_act_grad_cast through the inverse of a sub-pixel-major PixelShuffle(r) (the backward of conv -> PixelShuffle
+ * -> ReLU stored by KAIR_OUT_PSHUF_SPM with the activation in the epilogue): G fp32 and X (the post-activation image,
+ * x_dtype; kind 0 none, 1 ReLU, 2 LeakyReLU(slope)) are dense rows [B, H r, W r][C] of the shuffled image; out (dtype)
+ * and, when non-NULL, out_f32 are the pre-shuffle rows [B, H, W][r r C], column (i r + j) C + c <- pixel (y r + i,
+ * x r + j). */
+int kair_act_grad_punshuf(const float* G, const void* X, int x_dtype, void* out, int out_dtype, float* out_f32, int B,
+                          int H, int W, int C, int r, int kind, float slope, void* stream);
 /* Fused Adam (torch.optim.Adam maths, model_plain.py:210-222,302) + EMA (model_base.py:247-252)
  * over flat fp32 buffers.  lr_t is a DEVICE array {lr / (1 - beta1^t), sqrt(1 - beta2^t)} written by
  * the host before each (graph-replayed) step; ema may be NULL (E_decay = 0). */
@@ -817,6 +824,16 @@ int kair_synth_dn(const float* pool, int C, int Hs, int Ws, const int* params, i
                   unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
 int kair_synth_dn_map(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
                       int PS, unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
+/* kair_synth_dpsr replaces DatasetDPSR.__getitem__ train branch (data/dataset_dpsr.py) for a batch in ONE launch:
+ * kair_synth_sr's crop, augment and both bicubic passes (its banded kernel: with level 0 outL's image channels are
+ * kair_synth_sr's bytes), then per sample the level sigma_b = float bits in column scol of its parameter row (rows of
+ * pstride ints, pstride % 4 == 0 and >= 8, 16-byte aligned; columns 0-3 {image, rnd_h, rnd_w, mode} as kair_synth_sr's,
+ * clamped into the pool), L += sigma_b N(0, 1) (Philox keyed by (seed, step), counter = element index of the
+ * [B][C][PS/sf][PS/sf] block: kair_synth_dn_map's convention) and the level plane.  outH [B][C][PS][PS], outL
+ * [B][C + 1][PS/sf][PS/sf].  The pool is cropped to the scale; wh / ih hold Hs/sf rows of P taps, ww / iw Ws/sf rows. */
+int kair_synth_dpsr(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol, int B,
+                    int PS, int sf, const float* wh, const int* ih, const float* ww, const int* iw, int P,
+                    unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream);
 /* kair_synth_dn_level: DatasetFFDNet's train branch (data/dataset_ffdnet.py), kair_synth_dn_map's device code without
  * the map channel: outL [B][C][PS][PS] is kair_synth_dn_map's outL[:, :C] bit for bit (same params, seed, step), and
  * the level sigma_b goes to outC[b] ([B] fp32) instead. */

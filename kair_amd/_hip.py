@@ -197,6 +197,9 @@ _SIGS = {
     "kair_act_grad_cast": [c_vp, c_long, c_vp, c_int, c_long, c_vp, c_int, c_long, c_long, c_int, c_int, c_float, c_float,
                            c_vp],
     "kair_sumpool2x": [c_vp, c_long, c_vp, c_long, c_int, c_int, c_int, c_int, c_int, c_vp],
+    "kair_act_grad_punshuf": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_vp],
+    "kair_synth_dpsr": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                        c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_vp, c_vp, c_vp],
     "kair_adam_ema": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_float, c_float, c_float, c_float, c_float, c_vp],
     "kair_adam_ema_ex": [c_vp, c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_float, c_float, c_float, c_float, c_float, c_vp,
                          c_vp],
@@ -1007,6 +1010,17 @@ def sumpool2x(src, lds, dst, ldd, B, H, W, C, accumulate=False):
     check(lib().kair_sumpool2x(ptr(src), lds, ptr(dst), ldd, B, H, W, C, int(accumulate), stream_ptr()), "sumpool2x")
 
 
+def act_grad_punshuf(G, X, out, out_f32, B, H, W, C, r, kind, slope=0.0):
+    """act_grad_cast through the inverse of a sub-pixel-major PixelShuffle(r): G fp32 / X dense rows [B H r W r, C] of
+    the shuffled image -> out (and out_f32, or None) pre-shuffle rows [B H W, r r C]."""
+    n = B * H * r * W * r * C
+    if G.dtype != torch.float32 or G.numel() < n or (X is not None and X.numel() < n) or out.numel() < n or \
+            (out_f32 is not None and (out_f32.dtype != torch.float32 or out_f32.numel() < n)):
+        raise ValueError("act_grad_punshuf: a buffer is smaller than the image, or not fp32 where it must be")
+    check(lib().kair_act_grad_punshuf(ptr(G), ptr(X), dtype_code(X) if X is not None else F32, ptr(out), dtype_code(out),
+                                      ptr(out_f32), B, H, W, C, r, kind, slope, stream_ptr()), "act_grad_punshuf")
+
+
 def axpby_rows(y, ldy, x, ldx, M, C, a, b):
     """y[:, :C] = a * x[:, :C] + b * y[:, :C] over strided fp32 rows."""
     check(lib().kair_axpby_rows(ptr(y), ldy, ptr(x), ldx, M, C, a, b, stream_ptr()), "axpby_rows")
@@ -1151,6 +1165,30 @@ def synth_dn_map(pool, params, B, PS, seed, step, outH, outL, sigma_col=4):
     pp, ps = _sample_rows(params, B, max(5, sigma_col + 1), "synth_dn_map params")
     check(lib().kair_synth_dn_map(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, seed, step, ptr(outH), ptr(outL),
                                   stream_ptr()), "synth_dn_map")
+
+
+def synth_dpsr(pool, params, B, PS, sf, taps_h, taps_w, seed, step, outH, outL, sigma_col=4):
+    """DatasetDPSR batch (kair_synth_dpsr): params [B, 8] int32, {image, rnd_h, rnd_w, mode} as synth_sr's, the float32
+    bits of the sample's sigma / 255 in column sigma_col; the pool cropped to the scale, taps_h / taps_w synth_sr's;
+    outH [B, C, PS, PS], outL [B, C + 1, PS // sf, PS // sf]."""
+    require_device(pool, params, outH, outL, *taps_h, *taps_w)
+    N, C, Hs, Ws = _images(pool, "synth_dpsr: pool")
+    if sf not in (2, 3, 4) or PS % sf:
+        raise ValueError(f"synth_dpsr: scale 2, 3 or 4 and an H_size divisible by it (got scale {sf}, H_size {PS})")
+    if Hs % sf or Ws % sf or PS > Hs or PS > Ws:
+        raise ValueError(f"synth_dpsr: the pool ({Hs} x {Ws}) must be cropped to the scale and hold the patch ({PS})")
+    _fp32(outH, (B, C, PS, PS), "synth_dpsr: output")
+    _fp32(outL, (B, C + 1, PS // sf, PS // sf), "synth_dpsr: output")
+    pp, ps = _sample_rows(params, B, 8, "synth_dpsr params")
+    if ps % 4 or params.data_ptr() % 16 or not 4 <= sigma_col < ps:
+        raise ValueError("synth_dpsr params: 16-byte aligned rows of a multiple of 4 ints, the level column in 4 .. row")
+    (ih, wh), (iw, ww) = taps_h, taps_w
+    for t, n, d in ((ih, Hs // sf, torch.int32), (wh, Hs // sf, torch.float32), (iw, Ws // sf, torch.int32),
+                    (ww, Ws // sf, torch.float32)):
+        if t.dtype != d or t.dim() != 2 or t.shape != (n, wh.shape[1]) or not t.is_contiguous():
+            raise ValueError(f"synth_dpsr: taps must be contiguous [{n}, P] {d} tables of the pool's bicubic x1/{sf}")
+    check(lib().kair_synth_dpsr(ptr(pool), N, C, Hs, Ws, pp, ps, sigma_col, B, PS, sf, ptr(wh), ptr(ih), ptr(ww), ptr(iw),
+                                wh.shape[1], seed, step, ptr(outH), ptr(outL), stream_ptr()), "synth_dpsr")
 
 
 def synth_dn_level(pool, params, B, PS, seed, step, outH, outL, outC, sigma_col=4):

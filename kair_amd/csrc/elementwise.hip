@@ -1003,6 +1003,30 @@ __global__ void act_grad_cast_kernel(const float* __restrict__ G, long ldg, cons
   out[m * ldo + c] = (TO)g;
 }
 
+// act_grad_cast through the inverse of a sub-pixel-major PixelShuffle(r): G, X rows of the shuffled image
+// [B, H r, W r, C] (dense), out rows [B H W][r r C] with column (i r + j) C + c <- pixel (y r + i, x r + j).
+template <typename TX, typename TO>
+__global__ void act_grad_punshuf_kernel(const float* __restrict__ G, const TX* __restrict__ X, TO* __restrict__ out,
+                                        float* __restrict__ outf, long n, int H, int W, int C, int r, int kind,
+                                        float slope) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const long m = t / C;
+  const int c = (int)(t - m * C);
+  const long Wr = (long)W * r, HW = (long)H * r * Wr;
+  const long b = m / HW, p = m - b * HW;
+  const int Y = (int)(p / Wr), Xc = (int)(p - (long)Y * Wr);
+  const int y = Y / r, i = Y - y * r, x = Xc / r, j = Xc - x * r;
+  float g = G[t];
+  if (kind) {
+    const float xv = (float)X[t];
+    g = xv > 0.f ? g : (kind == 2 ? g * slope : 0.f);
+  }
+  const long o = ((b * H + y) * W + x) * ((long)r * r * C) + (long)(i * r + j) * C + c;
+  out[o] = (TO)g;
+  if (outf) outf[o] = g;
+}
+
 __global__ void sumpool2x_kernel(const float* __restrict__ src, long lds, float* __restrict__ dst, long ldd, int B, int H,
                                  int W, int C, int acc) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1557,6 +1581,34 @@ extern "C" int kair_act_grad_cast(const float* G, long ldg, const void* X, int x
     else
       KAIR_LAUNCH((act_grad_cast_kernel<float, float>), g, b, 0, s, G, ldg, (const float*)X, ldx, (float*)out, ldo,
                          M, C, kind, slope, scale);
+  }
+  KAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kair_act_grad_punshuf(const float* G, const void* X, int x_dtype, void* out, int out_dtype, float* out_f32,
+                                     int B, int H, int W, int C, int r, int kind, float slope, void* stream) {
+  KAIR_CHECK_ARG(G && out && B > 0 && H > 0 && W > 0 && C > 0 && r > 0 && kind >= 0 && kind <= 2 && (kind == 0 || X),
+                 "act_grad_punshuf: bad args");
+  KAIR_CHECK_ARG((x_dtype == KAIR_BF16 || x_dtype == KAIR_F32) && (out_dtype == KAIR_BF16 || out_dtype == KAIR_F32),
+                 "act_grad_punshuf: fp32 / bf16 rows only");
+  const long n = (long)B * H * r * W * r * C;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(nblk(n, 256)), b(256);
+  if (x_dtype == KAIR_BF16) {
+    if (out_dtype == KAIR_BF16)
+      KAIR_LAUNCH((act_grad_punshuf_kernel<bf16, bf16>), g, b, 0, s, G, (const bf16*)X, (bf16*)out, out_f32, n, H, W, C, r,
+                  kind, slope);
+    else
+      KAIR_LAUNCH((act_grad_punshuf_kernel<bf16, float>), g, b, 0, s, G, (const bf16*)X, (float*)out, out_f32, n, H, W, C,
+                  r, kind, slope);
+  } else {
+    if (out_dtype == KAIR_BF16)
+      KAIR_LAUNCH((act_grad_punshuf_kernel<float, bf16>), g, b, 0, s, G, (const float*)X, (bf16*)out, out_f32, n, H, W, C,
+                  r, kind, slope);
+    else
+      KAIR_LAUNCH((act_grad_punshuf_kernel<float, float>), g, b, 0, s, G, (const float*)X, (float*)out, out_f32, n, H, W, C,
+                  r, kind, slope);
   }
   KAIR_CHECK_LAUNCH();
   return 0;

@@ -68,19 +68,35 @@ __global__ __launch_bounds__(256) void synth_sr_kernel(const float* __restrict__
 // workgroups (a 4-patch batch would otherwise run on 12 CUs); each also writes its share of the
 // (augmented) H crop.  Outputs are addressed through the inverse augment map (dihedral: an
 // involution up to the transpose), so a band writes exactly the L pixels whose source row it holds.
-__global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restrict__ pool, int C, int Hs, int Ws,
-                                                           const int4* __restrict__ par, int PS, int sf,
-                                                           const float* __restrict__ wh, const int* __restrict__ ih,
-                                                           const float* __restrict__ ww, const int* __restrict__ iw, int P,
-                                                           int Wmax, int nband, float* __restrict__ outH,
-                                                           float* __restrict__ outL) {
+// DPSR (kair_synth_dpsr, DatasetDPSR): the same pair, then L = [L + sigma_b * N(0, 1) | sigma_b]: outL is
+// [B][C + 1][LS][LS], sigma_b the float in column scol of sample b's parameter row (rows of 4 pstr4 ints), the normals'
+// counter the element index of the [B][C][LS][LS] noisy block (kair_synth_dn_map's convention); channel 0's workgroups
+// write the level plane, one share per band.  sigma_b == 0 adds nothing, so L's image channels are task "sr"'s bytes.
+// The table's image and corner are clamped into the pool.
+template <bool DPSR>
+__global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restrict__ pool, int N, int C, int Hs, int Ws,
+                                                           const int4* __restrict__ par, int pstr4, int scol, int PS,
+                                                           int sf, const float* __restrict__ wh,
+                                                           const int* __restrict__ ih, const float* __restrict__ ww,
+                                                           const int* __restrict__ iw, int P, int Wmax, int nband,
+                                                           unsigned long long seed, unsigned long long step,
+                                                           float* __restrict__ outH, float* __restrict__ outL) {
   extern __shared__ float sV[];   // [rows of the band][Wmax]
   __shared__ int sLo, sHi;
   const int tid = threadIdx.x;
   const int sc = blockIdx.x / nband, band = blockIdx.x - sc * nband;
   const int b = sc / C, c = sc - (sc / C) * C;
-  const int4 pr = par[b];   // x = image, y = rnd_h (LQ rows), z = rnd_w, w = mode
+  int4 pr = par[(long)b * pstr4];   // x = image, y = rnd_h (LQ rows), z = rnd_w, w = mode
   const int LS = PS / sf;
+  float sigma = 0.f;
+  if (DPSR) {
+    sigma = __int_as_float(((const int*)par)[(long)b * pstr4 * 4 + scol]);
+    pr.x = min(max(pr.x, 0), N - 1);
+    pr.y = min(max(pr.y, 0), Hs / sf - LS);
+    pr.z = min(max(pr.z, 0), Ws / sf - LS);
+    pr.w &= 7;
+  }
+  const int CL = DPSR ? C + 1 : C;
   const int rpb = (LS + nband - 1) / nband, r0 = band * rpb, r1 = min(LS, r0 + rpb), nr = r1 - r0;
   const float* img = pool + ((long)pr.x * C + c) * Hs * Ws;
   // this band's share of the H crop
@@ -91,6 +107,11 @@ __global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restri
     int si, sj;
     aug_src(pr.w, i, j, PS, si, sj);
     oH[t] = img[(long)(pr.y * sf + si) * Ws + pr.z * sf + sj];
+  }
+  if (DPSR && c == 0) {   // this band's share of the level plane
+    float* oM = outL + ((long)b * CL + C) * LS * LS;
+    const int mpb = (LS * LS + nband - 1) / nband, m0 = band * mpb, m1 = min(LS * LS, m0 + mpb);
+    for (int t = m0 + tid; t < m1; t += 256) oM[t] = sigma;
   }
   if (nr <= 0) return;
   // source-column window of the horizontal taps of L columns pr.z .. pr.z + LS - 1
@@ -117,7 +138,7 @@ __global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restri
   }
   __syncthreads();
   // horizontal pass for source rows si in [r0, r1); output pixel through the inverse augment map
-  float* oL = outL + (long)(b * C + c) * LS * LS;
+  float* oL = outL + ((long)b * CL + c) * LS * LS;
   for (int t = tid; t < nr * LS; t += 256) {
     const int si = r0 + t / LS, sj = t - (t / LS) * LS;
     const int p = (pr.w & 2) ? LS - 1 - si : si, q = (pr.w & 4) ? LS - 1 - sj : sj;
@@ -125,6 +146,8 @@ __global__ __launch_bounds__(256) void synth_sr_sep_kernel(const float* __restri
     const int gx = pr.z + sj;
     float acc = 0.f;
     for (int bq = 0; bq < P; ++bq) acc = fmaf(ww[gx * P + bq], sV[(si - r0) * Wmax + iw[gx * P + bq] - lo], acc);
+    if (DPSR && sigma > 0.f)
+      acc += sigma * normal_at((unsigned long long)((((long)b * C + c) * LS + i) * LS + j), seed, step);
     oL[i * LS + j] = acc;
   }
 }
@@ -209,8 +232,8 @@ extern "C" int kair_synth_sr(const float* pool, int C, int Hs, int Ws, const int
   const int rpb = (LS + nband - 1) / nband;
   const size_t lds = (size_t)rpb * Wmax * sizeof(float);
   if (lds <= 60 * 1024) {
-    KAIR_LAUNCH(synth_sr_sep_kernel, dim3((unsigned)(B * C * nband)), dim3(256), lds, (hipStream_t)stream, pool, C,
-                       Hs, Ws, (const int4*)params, PS, sf, wh, ih, ww, iw, P, Wmax, nband, outH, outL);
+    KAIR_LAUNCH(synth_sr_sep_kernel<false>, dim3((unsigned)(B * C * nband)), dim3(256), lds, (hipStream_t)stream, pool,
+                0, C, Hs, Ws, (const int4*)params, 1, 0, PS, sf, wh, ih, ww, iw, P, Wmax, nband, 0ull, 0ull, outH, outL);
   } else {
     const long total = (long)B * C * PS * PS + (long)B * C * LS * LS;
     KAIR_LAUNCH(synth_sr_kernel, dim3((unsigned)nblocks(total)), dim3(256), 0, (hipStream_t)stream, pool, C, Hs, Ws,
@@ -262,4 +285,35 @@ extern "C" int kair_synth_dn_level(const float* pool, int N, int C, int Hs, int 
                                    float* outL, float* outC, void* stream) {
   return synth_dn_levels("synth_dn_level", false, pool, N, C, Hs, Ws, params, pstride, scol, B, PS, seed, step, outH, outL,
                          outC, stream);
+}
+
+// DatasetDPSR batches in one launch: kair_synth_sr's crop, augment and both bicubic passes (the banded separable
+// kernel, so L's image channels are its bytes), then per sample the level in column scol of its parameter row (rows
+// of pstride ints, pstride % 4 == 0; columns 0-3 {image, rnd_h, rnd_w, mode} as kair_synth_sr's), the AWGN (Philox
+// keyed by (seed, step), kair_synth_dn_map's convention) and the level plane.  outH [B][C][PS][PS], outL
+// [B][C + 1][PS/sf][PS/sf].  wh / ih hold Hs/sf rows of P taps, ww / iw Ws/sf rows.
+extern "C" int kair_synth_dpsr(const float* pool, int N, int C, int Hs, int Ws, const int* params, int pstride, int scol,
+                               int B, int PS, int sf, const float* wh, const int* ih, const float* ww, const int* iw, int P,
+                               unsigned long long seed, unsigned long long step, float* outH, float* outL, void* stream) {
+  KAIR_CHECK_ARG(pool && params && wh && ih && ww && iw && outH && outL, "synth_dpsr: null pointer");
+  KAIR_CHECK_ARG(N > 0 && C > 0 && Hs > 0 && Ws > 0 && B > 0 && sf > 0 && PS > 0 && PS % sf == 0 && P > 0,
+                 "synth_dpsr: bad sizes (N %d, C %d, %dx%d, B %d, PS %d, sf %d, P %d)", N, C, Hs, Ws, B, PS, sf, P);
+  KAIR_CHECK_ARG(Hs % sf == 0 && Ws % sf == 0, "synth_dpsr: the pool is not cropped to the scale");
+  KAIR_CHECK_ARG(PS <= Hs && PS <= Ws, "synth_dpsr: pool images smaller than the patch");
+  KAIR_CHECK_ARG(pstride >= 8 && pstride % 4 == 0 && scol >= 4 && scol < pstride,
+                 "synth_dpsr: level column %d outside rows of %d ints (a multiple of 4, >= 8)", scol, pstride);
+  KAIR_CHECK_ARG(((uintptr_t)params % 16) == 0, "synth_dpsr: the parameter table is not 16-byte aligned");
+  const int LS = PS / sf;
+  const int Wmax = (PS + 2 * P + 2 * sf) < Ws ? (PS + 2 * P + 2 * sf) : Ws;
+  int nband = 2048 / (B * C);
+  nband = nband < 1 ? 1 : (nband > LS ? LS : nband);
+  const int rpb = (LS + nband - 1) / nband;
+  const size_t lds = (size_t)rpb * Wmax * sizeof(float);
+  KAIR_CHECK_ARG(lds <= 60 * 1024, "synth_dpsr: a band of %d L rows x %d columns does not fit the staged pass", rpb, Wmax);
+  KAIR_CHECK_ARG((long)B * C * nband < (1L << 31), "synth_dpsr: too many workgroups");
+  KAIR_LAUNCH(synth_sr_sep_kernel<true>, dim3((unsigned)(B * C * nband)), dim3(256), lds, (hipStream_t)stream, pool, N, C,
+              Hs, Ws, (const int4*)params, pstride / 4, scol, PS, sf, wh, ih, ww, iw, P, Wmax, nband, seed, step, outH,
+              outL);
+  KAIR_CHECK_LAUNCH();
+  return 0;
 }

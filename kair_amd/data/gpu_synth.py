@@ -366,6 +366,47 @@ class _SRMD(_Task):
         return dict(zip(("L", "H"), next_batch(B)))
 
 
+class _DPSR(_SR):
+    """task="dpsr": DatasetDPSR batches (data/dataset_dpsr.py) for the DPSR prior: task "sr"'s pair, AWGN of one level
+    per sample on L, and the level as L's last channel.
+
+        synth = PatchSynth(pool, task="dpsr", scale=4, H_size=96, sigma=(0, 50), seed=0)
+        L, H = synth.next(16)                        # [B, C + 1, 24, 24], [B, C, 96, 96]
+        model.feed_data(synth.next_dict(16))         # the {"L", "H"} dict ModelPlain.feed_data reads
+
+    Per sample task "sr"'s four draws from the same generator -- so under one seed the crops and modes are task "sr"'s
+    -- and sigma = uniform(min, max) / 255 from a generator of its own (seeded by the task's seed).  One launch
+    (kair_synth_dpsr, csrc/synth.hip: kair_synth_sr's banded kernel with the noise, kair_synth_dn_map's Philox
+    convention, and the level plane).  `last_params` is the [B, 8] int32 table {image, rnd_h, rnd_w, mode}, the float32
+    bits of sigma / 255 (`last_params[:, 4:5].view(torch.float32)`), three unused columns."""
+    name, extra = "dpsr", 1
+
+    def options(self, scale=4, sigma=(0, 50)):
+        if scale not in (2, 3, 4):
+            raise ValueError(f"PatchSynth: task 'dpsr' takes scale 2, 3 or 4 (got {scale!r})")
+        if self.PS % scale:
+            raise ValueError(f"PatchSynth: H_size {self.PS} is not divisible by the scale {scale}")
+        super().options(scale)
+        self.sigma_range = tuple(float(v) for v in sigma) if isinstance(sigma, (tuple, list)) else (float(sigma),) * 2
+        if len(self.sigma_range) != 2 or not 0 <= self.sigma_range[0] <= self.sigma_range[1]:
+            raise ValueError(f"PatchSynth: task 'dpsr' takes sigma as (min, max), 0 <= min <= max (got {sigma!r})")
+        self.level_rng = None
+
+    def draw(self, B):
+        if self.level_rng is None:
+            self.level_rng = random.Random(self.seed * 2654435761 + 0xD95)
+        heads, sf = super().draw(B)
+        lev = [[self.level_rng.uniform(*self.sigma_range) / 255.0, 0.0, 0.0, 0.0] for _ in range(B)]
+        return _table(heads.tolist(), lev), sf
+
+    def fill(self, s, B, par, sf, Hp, Lp):
+        H.synth_dpsr(s.pool, par, B, self.PS, sf, self.taps_h, self.taps_w, self.seed, s.step, Hp, Lp)
+        return ()
+
+    def as_dict(self, next_batch, B):
+        return dict(zip(("L", "H"), next_batch(B)))
+
+
 class _BlindSR(_Task):
     """task="blindsr": DatasetBlindSR batches (data/dataset_blindsr.py; the BSRGAN degradation of BSRNet / BSRGAN and
     the real-world SwinIR) from a 3-channel pool.
@@ -448,8 +489,8 @@ TASKS = {"sr": _SR, "dn": _DN, "fdncnn": _FDnCNN, "ffdnet": _FFDNet, "jpeg": _JP
          "blindsr": _BlindSR}
 # TASKS is the set tests/test_patch_draws_cpu.py pins draw for draw against tables recorded before the task classes
 # existed (it asserts that its cases cover exactly TASKS); a task with no such recorded parent is registered here and
-# has its draws tested in a file of its own (tests/test_srmd_cpu.py)
-NEW_TASKS = {"srmd": _SRMD}
+# has its draws tested in a file of its own (tests/test_srmd_cpu.py, tests/test_ressr_cpu.py)
+NEW_TASKS = {"srmd": _SRMD, "dpsr": _DPSR}
 
 
 def patch_draws(task, N, C, Hs, Ws, H_size=96, seed=0, rank=0, world=1, **options):
@@ -511,7 +552,7 @@ class PatchSynth:
 
     def next_dict(self, B):
         """The next batch as the dict the task's model reads in feed_data: "usrnet" {"L", "H", "k", "sf", "sigma"}
-        (ModelPlain4), "fdncnn" and "srmd" {"L", "H"} (ModelPlain), "ffdnet" {"L", "H", "C"} (ModelPlain2); a ValueError
+        (ModelPlain4), "fdncnn", "srmd" and "dpsr" {"L", "H"} (ModelPlain), "ffdnet" {"L", "H", "C"} (ModelPlain2); a ValueError
         for the other tasks."""
         return self.kind.as_dict(self.next, B)
 

@@ -27,7 +27,9 @@ def define_Dataset(dataset_opt):
         from .dataset_blindsr import DatasetBlindSR as D
     elif t == "srmd":
         from .dataset_srmd import DatasetSRMD as D
+    elif t == "dpsr":   # the noisy bicubic LR image followed by its noise-level channel (train_dpsr.json)
+        from .dataset_dpsr import DatasetDPSR as D
     else:
         raise NotImplementedError(f"Dataset [{t}] is not on the kair_amd path (dncnn, fdncnn, drunet, ffdnet, sr, usrnet, jpeg, "
-                                  "blindsr, srmd).")
+                                  "blindsr, srmd, dpsr).")
     return D(dataset_opt)

@@ -75,7 +75,7 @@ class _Conv:
             self.Wd = torch.empty(Cip, 2 * _rup(9 * Cop, 64), device=dev, dtype=torch.float16) if need_dgrad else None
         else:
             self.Wd = torch.empty(Cip, 9 * Cop, device=dev, dtype=eng.tdt) if need_dgrad else None
-        self.bp = torch.empty(Cop, device=dev)
+        self.bp = torch.empty(Cop, device=dev) if self.b is not None else None   # bias=False: no bias pack
         self.wr = bool(wr) and Cop == 192 and Cip == 192 and self.split
         # wr_pair: an upsampling conv (64 -> 256, sub-pixel-major rows) reading a [hi | lo] pair image
         self.wr_pair = bool(wr) and not self.wr and tied_in and Cip == 64 and fcip == 128 and Cop == 256 and self.split
@@ -108,8 +108,10 @@ class _Conv:
         return H.rows(self.Wf, w_split=self.split)
 
     def pack_jobs(self):
-        w, b = self.w.detach(), self.b.detach()
-        jobs = [(w, self.Wf, self.mapf), (b, self.bp, self.mapb)]
+        w = self.w.detach()
+        jobs = [(w, self.Wf, self.mapf)]
+        if self.b is not None:
+            jobs.append((self.b.detach(), self.bp, self.mapb))
         if self.Wd is not None:
             jobs.append((w, self.Wd, self.mapd))
         if self.narrow:
@@ -321,6 +323,8 @@ class ConvEngineBase(EngineBase):
         """weight + bias gradient of conv c: dz [M, Cop] rows (compute dtype), src_op its im2col input;
         bias_src: the fp32 rows dz was cast from (bias gradient summed before rounding)."""
         self._wgrad(P, H.rows(dz, ld=ld_dz), src_op, M, c.Cop, 9 * c.Cip, c.map, grads[c.w])
+        if c.b is None:   # a conv without bias: no column sum, no gradient entry
+            return
         if bias_src is None:
             bias_src, ld_bias = dz, ld_dz
         H.colsum(H.rows(bias_src, ld=ld_bias), M, c.Cop, c.mapb, grads[c.b], P["colsum_ws"])

@@ -2,9 +2,10 @@
 
 `opt['netG']['net_type']` selects the network; constructor kwargs are taken from opt['netG'] under
 the reference's key names, and init_weights() runs when opt['is_train'] (select_network.py:268-272).
-Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet.  Everything else the
-reference's define_G knows (dpsr, msrresnet*, imdn, vrt, rvrt, ...) is out of
-scope for this build and raises NotImplementedError naming the type.
+Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet, msrresnet0, imdn, dpsr.
+Everything else the reference's define_G knows (msrresnet1 -- the bilinear-base MSRResNet kept upstream for the original
+checkpoints --, vrt, rvrt, ...) is out of scope for this build and raises NotImplementedError naming
+the type.
 """
 import functools
 import logging
@@ -13,7 +14,8 @@ from torch.nn import init
 
 logger = logging.getLogger("kair_amd")
 
-_ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "srmd", "rrdb", "rrdbnet", "usrnet", "drunet")
+_ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "srmd", "rrdb", "rrdbnet", "usrnet", "drunet", "msrresnet0", "imdn",
+            "dpsr")
 
 
 def define_G(opt):
@@ -56,6 +58,18 @@ def define_G(opt):
         from .network_unet import UNetRes
         net = UNetRes(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], act_mode=o["act_mode"],
                       downsample_mode=o["downsample_mode"], upsample_mode=o["upsample_mode"], **ek)
+    elif t in ("msrresnet0", "imdn", "dpsr"):   # the residual SR networks on ResSREngine, trained by ModelPlain
+        if t == "msrresnet0":
+            from .network_msrresnet import MSRResNet0 as cls
+        elif t == "imdn":
+            from .network_imdn import IMDN as cls
+        else:   # the LR image followed by one noise-level channel
+            from .network_dpsr import MSRResNet_prior as cls
+        net = cls(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], upscale=o["scale"],
+                  act_mode=o["act_mode"], upsample_mode=o["upsample_mode"], **ek)
+    elif t == "msrresnet1":
+        raise NotImplementedError("netG [msrresnet1] (the bilinear-base MSRResNet kept upstream for the original "
+                                  "checkpoints) is not on the kair_amd MI355X path; msrresnet0 is")
     else:
         raise NotImplementedError("netG [{:s}] is not on the kair_amd MI355X path (supported: {})".format(
             t, ", ".join(_ON_PATH)))
