@@ -968,6 +968,32 @@ int kair_bsr_ops(const float* src, float* dst, int B, int Hmax, int Wmax, const 
 int kair_jpeg_roundtrip_var(const float* x, int N, int Hmax, int Wmax, const int* hw, int hwstride, int w_min,
                             const int* quality, int qstride, float* out, void* workspace, void* stream);
 
+/* SCUNet (Swin-Conv-UNet, csrc/scunet.hip): the transformer branch runs at head dim 32 = head pad, so the q/k/v
+ * layouts have no pad column for a ones column.
+ * kair_qkvblk_colsum: bias_grad[(part*nh + h)*hd + d] (+)= sum over windows and tokens of the head-blocked
+ * dqkv [3][nWin][nh][64][32] (fp32 or bf16) that kair_window_attn_bwd_w writes (window 8, head pad 32), hd <= 32:
+ * the gradient of the q/k/v Linear's bias in its reference order (q heads, k heads, v heads).  ws:
+ * kair_qkvblk_colsum_ws(nh) floats.  Fixed summation order.
+ * kair_table_transpose: dst[c][r] (+)= src[r][c] for an R x C fp32 table -- the relative-position gradient
+ * [(2ws-1)^2][nh] of kair_window_attn_bwd_w into the [nh][2ws-1][2ws-1] layout of SCUNet's relative_position_params. */
+long kair_qkvblk_colsum_ws(int nh);
+int kair_qkvblk_colsum(const void* dqkv, int dtype, long nWin, int nh, int hd, float* ws, float* bias_grad,
+                       int accumulate, void* stream);
+int kair_table_transpose(const float* src, float* dst, int R, int C, int accumulate, void* stream);
+/* SCUNet's narrow transformer Block in one launch (bf16 operands, fp32 accumulation; trans_dim C = 32 or 64, heads of 32,
+ * window 8), one workgroup per window of the B x H x W token grid:
+ *   mid = x + linear(W-MSA(LN1(x)));  out = mid + fc2(gelu(fc1(LN2(mid))))
+ * x / out: fp32 token rows (row strides ldx / ldo; out may be x: each workgroup reads its window's rows before it writes
+ * them), addressed through the window map of `shift` (0, or 4 with the analytic region mask, -100); the weights are the
+ * bf16 [N][K] row packs of kair_gemm_nt (wqkv [3C][C] in q-heads, k-heads, v-heads order, wproj [C][C], w1 [4C][C],
+ * w2 [C][4C]), biases and LayerNorm parameters fp32, table fp32 [(2ws-1)^2][C/32].  Inference only: nothing is kept for
+ * a backward.  The arithmetic is the unfused sequence's (kair_layernorm_fwd, kair_gemm_nt, kair_window_attn_fwd_w). */
+int kair_scu_block_fwd(const float* x, long ldx, float* out, long ldo, const float* gamma1, const float* beta1,
+                       const float* gamma2, const float* beta2, float eps, const void* wqkv, const float* bqkv,
+                       const void* wproj, const float* bproj, const void* w1, const float* b1, const void* w2,
+                       const float* b2, const float* table, float scale, int B, int H, int W, int C, int shift,
+                       void* stream);
+
 const char* kair_last_error(void);
 int kair_device_arch(char* buf, int len);
 

@@ -274,6 +274,11 @@ _SIGS = {
                                 c_int, c_int, c_int, c_int, c_vp],
     "kair_window_attn_bwd_x3": [c_vp, c_vp, c_vp, c_vp, c_long, c_vp, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
                                 c_vp, c_long, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_vp],
+    "kair_qkvblk_colsum_ws": [c_int],
+    "kair_qkvblk_colsum": [c_vp, c_int, c_long, c_int, c_int, c_vp, c_vp, c_int, c_vp],
+    "kair_table_transpose": [c_vp, c_vp, c_int, c_int, c_int, c_vp],
+    "kair_scu_block_fwd": [c_vp, c_long, c_vp, c_long, c_vp, c_vp, c_vp, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                           c_vp, c_vp, c_vp, c_float, c_int, c_int, c_int, c_int, c_int, c_vp],
     "kair_last_error": [],
     "kair_device_arch": [ctypes.c_char_p, c_int],
 }
@@ -282,7 +287,8 @@ _RESTYPE = {"kair_gemm_nt_x3_lnbwd_parts": c_long, "kair_layernorm_bwd_blocks": 
             "kair_conv3x3_narrow_dgrad_ws": c_long, "kair_conv3x3_narrow_x3_ws": c_long,
             "kair_jpeg_workspace_bytes": c_long, "kair_ssim_workspace_bytes": c_long,
             "kair_grad_norm_ws": c_long, "kair_image_metrics_workspace_bytes": c_long,
-            "kair_psnr_db_ref": ctypes.c_double}
+            "kair_psnr_db_ref": ctypes.c_double,
+            "kair_qkvblk_colsum_ws": c_long}
 
 _lib = None
 
@@ -1526,3 +1532,41 @@ def rowgemm_lnbwd(A, M, K, W, x, gamma, mean, rstd, C, D, part, win=(0, 0, 0, 0)
                                    ptr(rstd), C, ptr(D), D.stride(0), *win,
                                    ctypes.byref(copy) if copy is not None else None, ptr(part), stream_ptr()),
           "rowgemm_lnbwd")
+
+
+def qkvblk_colsum_ws(nh):
+    return lib().kair_qkvblk_colsum_ws(nh)
+
+
+def qkvblk_colsum(dqkv, nWin, nh, hd, ws, bias_grad, accumulate=False):
+    """bias_grad [3 * nh * hd] (+)= the column sums of the head-blocked dqkv [3][nWin][nh][64][32] (kair_qkvblk_colsum)."""
+    if dqkv.numel() < 3 * nWin * nh * 64 * 32 or ws.numel() < qkvblk_colsum_ws(nh) or bias_grad.numel() < 3 * nh * hd:
+        raise ValueError("qkvblk_colsum: a buffer is smaller than the geometry")
+    check(lib().kair_qkvblk_colsum(ptr(dqkv), dtype_code(dqkv), nWin, nh, hd, ptr(ws), ptr(bias_grad), int(accumulate),
+                                   stream_ptr()), "qkvblk_colsum")
+
+
+def table_transpose(src, dst, R, C, accumulate=False):
+    """dst [C][R] (+)= src [R][C]^T, fp32 (kair_table_transpose)."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float32 or src.numel() < R * C or dst.numel() < R * C:
+        raise ValueError("table_transpose: fp32 tables of R * C elements")
+    check(lib().kair_table_transpose(ptr(src), ptr(dst), R, C, int(accumulate), stream_ptr()), "table_transpose")
+
+
+def scu_block_fwd(x, ldx, out, ldo, ln1, ln2, wqkv, bqkv, wproj, bproj, w1, b1, w2, b2, table, scale, B, H, W, C, shift):
+    """SCUNet's narrow transformer Block in one launch (kair_scu_block_fwd): x / out fp32 token rows [B*H*W, ld] (out may
+    be x), ln1 / ln2 the LayerNorm modules, the weights bf16 [N][K] row packs, biases and table [(2ws-1)^2][C/32] fp32."""
+    M = B * H * W
+    for w, shape in ((wqkv, (3 * C, C)), (wproj, (C, C)), (w1, (4 * C, C)), (w2, (C, 4 * C))):
+        if w.dtype != torch.bfloat16 or tuple(w.shape) != shape or not w.is_contiguous():
+            raise ValueError(f"scu_block_fwd: a weight pack is not a contiguous bf16 {shape}")
+    for b, n in ((bqkv, 3 * C), (bproj, C), (b1, 4 * C), (b2, C), (ln1.weight, C), (ln1.bias, C), (ln2.weight, C),
+                 (ln2.bias, C), (table, 225 * (C // 32))):
+        if b.dtype != torch.float32 or b.numel() != n:
+            raise ValueError("scu_block_fwd: a bias / LayerNorm / table operand has the wrong size or dtype")
+    for t, ld in ((x, ldx), (out, ldo)):
+        if t.dtype != torch.float32 or ld < C or t.storage_offset() + (M - 1) * ld + C > t.untyped_storage().nbytes() // 4:
+            raise ValueError("scu_block_fwd: x / out rows exceed their buffer")
+    check(lib().kair_scu_block_fwd(ptr(x), ldx, ptr(out), ldo, ptr(ln1.weight), ptr(ln1.bias), ptr(ln2.weight), ptr(ln2.bias),
+                                   ln1.eps, ptr(wqkv), ptr(bqkv), ptr(wproj), ptr(bproj), ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                   ptr(table), scale, B, H, W, C, shift, stream_ptr()), "scu_block_fwd")

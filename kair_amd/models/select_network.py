@@ -2,7 +2,8 @@
 
 `opt['netG']['net_type']` selects the network; constructor kwargs are taken from opt['netG'] under
 the reference's key names, and init_weights() runs when opt['is_train'] (select_network.py:268-272).
-Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet, msrresnet0, imdn, dpsr.
+Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet, msrresnet0, imdn, dpsr,
+scunet.
 Everything else the reference's define_G knows (msrresnet1 -- the bilinear-base MSRResNet kept upstream for the original
 checkpoints --, vrt, rvrt, ...) is out of scope for this build and raises NotImplementedError naming
 the type.
@@ -15,7 +16,7 @@ from torch.nn import init
 logger = logging.getLogger("kair_amd")
 
 _ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "srmd", "rrdb", "rrdbnet", "usrnet", "drunet", "msrresnet0", "imdn",
-            "dpsr")
+            "dpsr", "scunet")
 
 
 def define_G(opt):
@@ -67,6 +68,10 @@ def define_G(opt):
             from .network_dpsr import MSRResNet_prior as cls
         net = cls(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], upscale=o["scale"],
                   act_mode=o["act_mode"], upsample_mode=o["upsample_mode"], **ek)
+    elif t == "scunet":   # the Swin-Conv-UNet denoiser, trained by ModelPlain ('plain'); bf16 / fp32 engines
+        from .network_scunet import SCUNet
+        net = SCUNet(in_nc=o["in_nc"], config=o["config"], dim=o["dim"], drop_path_rate=o.get("drop_path_rate") or 0.0,
+                     input_resolution=o["input_resolution"], **ek)
     elif t == "msrresnet1":
         raise NotImplementedError("netG [msrresnet1] (the bilinear-base MSRResNet kept upstream for the original "
                                   "checkpoints) is not on the kair_amd MI355X path; msrresnet0 is")
