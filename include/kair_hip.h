@@ -91,6 +91,12 @@ typedef struct {
                           x3 compute: the lo plane of an fp16 operand                           */
   int x3_exp;          /* x3 compute: the operand's power-of-2 exponent (fp32: applied before the fp16
                           split; fp16 planes: carried by the stored values); packed weights KAIR_X3_WEXP */
+  int im_dil;          /* IM2COL3: the conv's dilation (padding = dilation): tap (dy, dx) reads pixel
+                          (y + im_dil dy, x + im_dil dx), im_flip negating the offsets as without it.  0 / 1 =
+                          none; 2..4 valid, anything else KAIR_ERR_ARG, as is im_dil > 1 with im_up == 2 or
+                          under KAIR_COMPUTE_X3.  Read by the address-computing loaders of kair_gemm_nt (A) and
+                          kair_gemm_tn (B); every kernel specialised for the +-1 taps (the halo conv, the
+                          tap-per-tile weight-gradient rings, a_copy) declines a dilated operand */
 } kair_operand;
 
 typedef enum {
@@ -492,6 +498,18 @@ int kair_conv3x3_wr_ex(const void* x, int x_dtype, long ldx, int split, int flip
                        const float* bias, const float* resid, long ldr, void* out, int out_dtype, long ldo, void* out_lo,
                        int ps_r, int act, float slope, const void* gate, long ldg, void* acopy, long ldac, int acones,
                        int B, int H, int W, int C, int N, void* stream);
+
+/* Dilated 3x3 conv, stride 1, padding = dilation = dil in 2..4, C = N = 64 (csrc/conv_dil.hip; IRCNN's body convs
+ * and their input gradients): 8 x 16-pixel tiles with a (8 + 2 dil) x (16 + 2 dil) halo in LDS, weights streamed into
+ * registers as in kair_conv3x3_wr, one bf16 product, fp32 accumulation.  x: bf16 NHWC rows [B*H*W][ldx]; any H, W >= 1
+ * (edge tiles mask their stores, pixels outside an image read as zero).  w_kind 15: the forward pack (its hi halves,
+ * bf16(w), are read); w_kind 16 with flip = 1: the input gradient over the output-gradient rows.  out[m][n] =
+ * act(conv + bias[n]), act KAIR_ACT_NONE / RELU / LEAKY(slope), fp32 or bf16 rows of stride ldo (columns >= 64 are
+ * not written).  Anything outside the contract is KAIR_ERR_ARG (kair_conv3x3_dil_ok: 1 inside it, 0 outside); such a
+ * conv runs as kair_gemm_nt over an IM2COL3 operand with im_dil. */
+int kair_conv3x3_dil_ok(int dil, int C, int N);
+int kair_conv3x3_dil(const void* x, long ldx, int dil, int flip, const void* w, int w_kind, const float* bias, int act,
+                     float slope, void* out, int out_dtype, long ldo, int B, int H, int W, int C, int N, void* stream);
 
 /* kair_conv3x3_wr's split form in the fp16-pair arithmetic of KAIR_COMPUTE_X3 (the fp32x3 engine's 192 -> 192
  * convs and their input gradients, instead of kair_gemm_nt over KAIR_LD_IM2COL3): x fp32 NHWC rows; the kernel

@@ -37,7 +37,8 @@ class Operand(ctypes.Structure):
                 ("im_H", c_int), ("im_W", c_int), ("im_C", c_int), ("im_flip", c_int),
                 ("qkv_nh", c_int), ("qkv_hdp", c_int), ("qkv_tok", c_int),
                 ("rowscale", c_vp), ("rows_per_scale", c_int), ("ones_col", c_int), ("ones_in_data", c_int),
-                ("im_up", c_int), ("w_split", c_int), ("a_split", c_int), ("lo_ptr", c_vp), ("x3_exp", c_int)]
+                ("im_up", c_int), ("w_split", c_int), ("a_split", c_int), ("lo_ptr", c_vp), ("x3_exp", c_int),
+                ("im_dil", c_int)]
 
 
 class CopyDesc(ctypes.Structure):
@@ -162,6 +163,9 @@ _SIGS = {
     "kair_conv3x3_wr_ex": [c_vp, c_int, c_long, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_int, c_long, c_vp,
                            c_int, c_int, c_float, c_vp, c_long, c_vp, c_long, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_vp],
+    "kair_conv3x3_dil_ok": [c_int, c_int, c_int],
+    "kair_conv3x3_dil": [c_vp, c_long, c_int, c_int, c_vp, c_int, c_vp, c_int, c_float, c_vp, c_int, c_long, c_int, c_int,
+                         c_int, c_int, c_int, c_vp],
     "kair_conv3x3_wr_x3_tile": [c_int, c_int, c_int, c_int, c_int],
     "kair_conv3x3_wr_x3": [c_vp, c_long, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_long, c_vp, c_long, c_int, c_int, c_int,
                            c_int, c_int, c_vp],
@@ -379,11 +383,12 @@ def asplit(op, lo=None, pair=False):
     return op
 
 
-def im2col(t, H, W, C, flip=False, ones_col=-1, ld=None, up=1, ones_in_data=False):
+def im2col(t, H, W, C, flip=False, ones_col=-1, ld=None, up=1, ones_in_data=False, dil=1):
     """3x3 / pad 1 im2col view of an NHWC map: H x W is the CONV grid, ld the pixel stride
     (default C), up=2 reads the source (H/2 x W/2) through a nearest x2 upsample.  ones_in_data: the
     map already holds 1.0 in channel ones_col % C of every pixel (read through the center tap,
-    ones_col = 4 * C + c, by the tap-per-tile weight-gradient ring)."""
+    ones_col = 4 * C + c, by the tap-per-tile weight-gradient ring).  dil: the conv's dilation (padding =
+    dilation, 1..4; kair_operand.im_dil): tap (dy, dx) reads pixel (y + dil dy, x + dil dx)."""
     o = Operand()
     o._keep = t
     o.ptr = ptr(t)
@@ -392,6 +397,7 @@ def im2col(t, H, W, C, flip=False, ones_col=-1, ld=None, up=1, ones_in_data=Fals
     o.ld = ld if ld is not None else C
     o.im_H, o.im_W, o.im_C, o.im_flip = H, W, C, int(flip)
     o.im_up = up
+    o.im_dil = 0 if dil == 1 else dil   # 1: the field stays as every earlier caller left it
     o.ones_col = ones_col
     o.ones_in_data = int(ones_in_data)
     o.rows_per_scale = 1
@@ -751,6 +757,19 @@ def conv3x3_wr(x, ldx, flip, w, bias, resid, out, B, H, W, C, N, ldr=None, ldo=N
                                    act, slope, ptr(gate), ldg if ldg is not None else (gate.shape[-1] if gate is not None else 0),
                                    ptr(acopy), ldac if ldac is not None else (acopy.shape[-1] if acopy is not None else 0),
                                    acones, B, H, W, C, N, stream_ptr()), "conv3x3_wr")
+
+
+def conv3x3_dil_ok(dil, C, N):
+    """Whether kair_conv3x3_dil takes this conv (dilation 2..4, C = N = 64)."""
+    return bool(lib().kair_conv3x3_dil_ok(dil, C, N))
+
+
+def conv3x3_dil(x, ldx, dil, flip, w, w_kind, bias, out, B, H, W, C, N, ldo=None, act=ACT_NONE, slope=0.0):
+    """Dilated 3x3 conv over bf16 NHWC rows (csrc/conv_dil.hip): w = pack kind 15 (forward) or 16 (flip = 1: input
+    gradient); out fp32 or bf16 rows of stride ldo."""
+    check(lib().kair_conv3x3_dil(ptr(x), ldx, dil, int(flip), ptr(w), w_kind, ptr(bias), act, slope, ptr(out),
+                                 dtype_code(out), ldo if ldo is not None else out.shape[-1], B, H, W, C, N, stream_ptr()),
+          "conv3x3_dil")
 
 
 def conv3x3_wr_x3_tile(B, H, W, C, N):

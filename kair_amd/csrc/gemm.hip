@@ -1407,7 +1407,7 @@ static int halo_bm_of(int H, int W, int C, int N, const Epi& e) {
 template <typename TA>
 static bool conv_halo_ok(const Op& A, const Op& B, const Epi& e, long M, int N, int K) {
   const int H = A.imH, W = A.imW, C = A.imC;
-  if (A.up_sh != 0 || C % HC_BK != 0 || C > 256 || K != 9 * C || N > 256 || N % 4 != 0) return false;
+  if (A.up_sh != 0 || A.dil != 1 || C % HC_BK != 0 || C > 256 || K != 9 * C || N > 256 || N % 4 != 0) return false;
   // C in (192, 256]: channel-group passes, plain bf16 operands, 64 outputs
   if (C > 192 && (C != 256 || sizeof(TA) != 2 || A.asplit || B.wsplit || N > 64 || e.resid || e.acopy)) return false;
   // the two-pass split forms lo from an fp32 image; a bf16 image carries it as its [hi | lo] halves (a_split 2)
@@ -1637,6 +1637,8 @@ int kair_check_operand(const kair_operand* o, const char* what) {
     KAIR_CHECK_ARG(o->ld == 0 || (o->ld >= o->im_C && (o->ld * esz) % 16 == 0), "%s: im2col pixel stride", what);
     KAIR_CHECK_ARG(o->im_up == 0 || o->im_up == 1 || (o->im_up == 2 && o->im_H % 2 == 0 && o->im_W % 2 == 0),
                    "%s: im2col upsample factor", what);
+    KAIR_CHECK_ARG(o->im_dil >= 0 && o->im_dil <= 4, "%s: im2col dilation %d (0 / 1 none, 2..4)", what, o->im_dil);
+    KAIR_CHECK_ARG(o->im_dil <= 1 || o->im_up != 2, "%s: no dilated im2col through the x2 upsample", what);
   }
   if (o->mode == KAIR_LD_S2D) {
     KAIR_CHECK_ARG(o->im_C % 8 == 0 && o->im_H > 0 && o->im_W > 0, "%s: space-to-depth geometry", what);
@@ -1675,6 +1677,8 @@ extern "C" int kair_gemm_nt(const kair_operand* A, const kair_operand* B, const 
     KAIR_CHECK_ARG(E->out_ones_col_p1 <= 0 || rows,
                    "gemm_nt: out_ones_col_p1 is read only by the ROWS store (out_mode %d)", om);
   }
+  KAIR_CHECK_ARG(compute != KAIR_COMPUTE_X3 || A->mode != KAIR_LD_IM2COL3 || A->im_dil <= 1,
+                 "gemm_nt: no fp32x3 form of a dilated im2col operand");
   if (compute == KAIR_COMPUTE_X3) return kair_gemm_nt_x3(A, B, E, M, N, K, stream);   // gemm_x3.hip
   KAIR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0, "gemm_nt: bad M/N/K (%ld,%d,%d), K%%8 must be 0", M, N, K);
   KAIR_CHECK_ARG(B->mode == KAIR_LD_ROWS && B->dtype == compute && B->win_ws == 0,
@@ -1772,6 +1776,8 @@ extern "C" int kair_gemm_tn(const kair_operand* A, const kair_operand* B, float*
   KAIR_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && splits > 0, "gemm_tn: bad sizes");
   KAIR_CHECK_ARG(A->mode != KAIR_LD_IM2COL3 && A->mode != KAIR_LD_S2D, "gemm_tn: A cannot be im2col / space-to-depth");
   KAIR_CHECK_ARG(B->mode != KAIR_LD_QKVBLK, "gemm_tn: B cannot be q/k/v blocked");
+  KAIR_CHECK_ARG(compute != KAIR_COMPUTE_X3 || B->mode != KAIR_LD_IM2COL3 || B->im_dil <= 1,
+                 "gemm_tn: no fp32x3 form of a dilated im2col operand");
   if (compute == KAIR_COMPUTE_X3) return kair_gemm_tn_x3(A, B, ws, splits, M, N, K, stream);   // gemm_x3.hip
   KAIR_CHECK_ARG(compute == KAIR_BF16 || (A->dtype == KAIR_F32 && B->dtype == KAIR_F32),
                  "gemm_tn: fp32 compute needs fp32 operands");
@@ -1800,7 +1806,7 @@ extern "C" int kair_gemm_tn(const kair_operand* A, const kair_operand* B, float*
   }
   // conv weight gradient, bf16 rows x bf16 192-channel image (ones column, if any, stored in the data)
   if (g_ring_mode && compute == KAIR_BF16 && tn_tap_shape(M, N, K) && A->dtype == KAIR_BF16 && B->dtype == KAIR_BF16 &&
-      A->mode == KAIR_LD_ROWS && B->mode == KAIR_LD_IM2COL3 && B->im_C == TNR_BK && !B->im_flip && B->im_up <= 1 &&
+      A->mode == KAIR_LD_ROWS && B->mode == KAIR_LD_IM2COL3 && B->im_C == TNR_BK && !B->im_flip && B->im_up <= 1 && B->im_dil <= 1 &&
       !A->rowscale && !B->rowscale && A->win_ws == 0 && A->ones_col < 0 && (B->ones_col < 0 || B->ones_in_data) &&
       A->ld % 8 == 0 && b.ld % 8 == 0 && (long)B->im_H * B->im_W > 0 && M % ((long)B->im_H * B->im_W) == 0) {
     const int tilesN = (N + TNR_BN - 1) / TNR_BN, tilesK = 9;
@@ -1818,7 +1824,7 @@ extern "C" int kair_gemm_tn(const kair_operand* A, const kair_operand* B, float*
   // per im2col column block
   if (g_ring_mode && compute == KAIR_BF16 && tn_ring_shape(M, N, K) && K == 9 * 64 && A->dtype == KAIR_BF16 &&
       B->dtype == KAIR_BF16 && A->mode == KAIR_LD_ROWS && B->mode == KAIR_LD_IM2COL3 && B->im_C == 64 && !B->im_flip &&
-      B->im_up <= 1 && !A->rowscale && !B->rowscale && A->win_ws == 0 && A->ones_col < 0 && B->ones_col < 0 &&
+      B->im_up <= 1 && B->im_dil <= 1 && !A->rowscale && !B->rowscale && A->win_ws == 0 && A->ones_col < 0 && B->ones_col < 0 &&
       A->ld % 8 == 0 && b.ld % 8 == 0 && (long)B->im_H * B->im_W > 0 && M % ((long)B->im_H * B->im_W) == 0) {
     const int tilesN = (N + TNR_BN - 1) / TNR_BN, tilesK = 3;
     const int ntiles = tilesN * tilesK;

@@ -21,6 +21,7 @@ struct Op {
   WinMap win;
   int imH, imW, imC, flip;
   int up_sh;   // IM2COL: log2 of the nearest-upsample factor (source image imH>>up_sh x imW>>up_sh)
+  int dil;     // IM2COL: tap step in pixels (kair_operand.im_dil; 1 = none)
   int nh, hdp, tok;
   const float* rowscale;
   int rps;
@@ -41,6 +42,7 @@ Op make_op(const kair_operand& o, long M) {
   op.win = make_winmap(o.win_H, o.win_W, o.win_ws, o.win_shift);
   op.imH = o.im_H; op.imW = o.im_W; op.imC = o.im_C; op.flip = o.im_flip;
   op.up_sh = o.im_up == 2 ? 1 : 0;
+  op.dil = o.im_dil > 1 ? o.im_dil : 1;
   if ((o.mode == KAIR_LD_IM2COL3 || o.mode == KAIR_LD_S2D) && op.ld == 0) op.ld = o.im_C;
   op.nh = o.qkv_nh; op.hdp = o.qkv_hdp; op.tok = o.qkv_tok;
   op.rowscale = o.rowscale; op.rps = o.rows_per_scale > 0 ? o.rows_per_scale : 1;
@@ -156,7 +158,7 @@ KAIR_DEV void issue_chunk(const Op& op, const RowState& r, int k, int K, Raw<T>&
     const int c = k - tap * op.imC;
     int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
     if (op.flip) { dy = -dy; dx = -dx; }
-    const int y = r.y + dy, x = r.x + dx;
+    const int y = r.y + dy * op.dil, x = r.x + dx * op.dil;
     ok = ok && y >= 0 && y < op.imH && x >= 0 && x < op.imW;
     off = (r.base + (long)(y >> op.up_sh) * (op.imW >> op.up_sh) + (x >> op.up_sh)) * op.ld + c;
   } else if constexpr (AM == AM_S2D) {

@@ -34,7 +34,7 @@ class _Conv:
     (DESIGN.md "parity at bf16"); activation rounding is unbiased and averages out."""
 
     def __init__(self, eng, mod, Cop, Cip, need_dgrad=True, split=None, n_perm=0, tied_in=False, fwd_cip=None,
-                 narrow=False, wr=False):
+                 narrow=False, wr=False, dil=1, dil_kernel=False):
         """n_perm = r*r: output channels stored sub-pixel-major for a following PixelShuffle(r)
         (kair_wmap.n_perm; the KAIR_OUT_PSHUF_SPM / PUNSHUF_SPM epilogues store 16 bytes at a time).
         tied_in: the forward form repeats the input channels in both halves of Cip (kair_wmap kG = 2),
@@ -45,7 +45,9 @@ class _Conv:
         narrow: a 64 -> NR <= 4 conv run by the narrow-output kernels (kair_conv3x3_narrow_*): its forward
         form is pack kind 15 (16x16x32 fragment order, hi/lo halves), the backward reads the fp32 weight.
         wr: a 192 -> 192 conv also packed for kair_conv3x3_wr: forward pack kind 15, input gradient kind 16
-        (fp32x3: kair_conv3x3_wr_x3's fp16 pairs, kinds 22 / 23)."""
+        (fp32x3: kair_conv3x3_wr_x3's fp16 pairs, kinds 22 / 23).
+        dil: the conv's dilation (padding = dilation); dil_kernel: also pack a dilated conv inside kair_conv3x3_dil's
+        contract (plain bf16, dil 2..4, 64 -> 64) for that kernel: forward kind 15, input gradient kind 16."""
         self.w, self.b = mod.weight, mod.bias
         Co, Ci = self.w.shape[:2]
         self.Co, self.Ci, self.Cop, self.Cip = Co, Ci, Cop, Cip
@@ -92,6 +94,14 @@ class _Conv:
             self.Wc15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
             self.mapc16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
             self.Wc16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16)
+        self.dil = int(dil)
+        self.dil_fast = (bool(dil_kernel) and self.dil > 1 and eng.tdt == torch.bfloat16 and not self.split and
+                         not n_perm and not tied_in and H.conv3x3_dil_ok(self.dil, Cip, Cop))
+        if self.dil_fast:
+            self.mapk15 = H.wmap(15, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wk15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.bfloat16)
+            self.mapk16 = H.wmap(16, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
+            self.Wk16 = torch.empty(Cip * 9 * Cop, device=dev, dtype=torch.bfloat16) if need_dgrad else None
         if self.wr and self.x3:   # fp16 pairs of w 2^KAIR_X3_WEXP in fragment order (same element counts)
             self.map15 = H.wmap(22, Co, Ci, (1, Co, Cop), (1, Ci, Cip))
             self.Wf15 = torch.empty(Cop * 2 * 9 * Cip, device=dev, dtype=torch.float16)
@@ -122,6 +132,10 @@ class _Conv:
             jobs += [(w, self.Wp15, self.mapp), (w, self.Wp16, self.mapp16)]
         if self.wr_n64:
             jobs += [(w, self.Wc15, self.mapc), (w, self.Wc16, self.mapc16)]
+        if self.dil_fast:
+            jobs.append((w, self.Wk15, self.mapk15))
+            if self.Wk16 is not None:
+                jobs.append((w, self.Wk16, self.mapk16))
         return jobs
 
 

@@ -1,7 +1,8 @@
 """DnCNN / FDnCNN / FFDNet / SRMD step program for MI355X.
 
 Reference: /root/reference/models/network_dncnn.py:40-71 (DnCNN, out = x - model(x)), 128-149
-(FDnCNN, out = model(x)); layers from basicblock.conv (basicblock.py:61-98).  SURVEY §8 row a14.
+(FDnCNN, out = model(x)); layers from basicblock.conv (basicblock.py:61-98).  SURVEY §8 row a14.  IRCNN, the same
+file's third class (restated in network_dncnn.IRCNN), is the same loop with a dilation per conv.
 
 Per body layer: implicit-GEMM 3x3 conv (bias in the epilogue) -> fp32 pre-norm rows z ->
 BatchNorm (batch statistics + running-stat update in train mode, running statistics in eval) with
@@ -24,16 +25,24 @@ from .base import ConvEngineBase, _Conv, _rup
 class DnCNNEngine(ConvEngineBase):
     COMPUTE_DTYPES = ("bf16", "fp32")
 
-    def __init__(self, net, compute_dtype="bf16", residual=True):
+    def __init__(self, net, compute_dtype="bf16", residual=True, dil_kernel=True):
+        """dil_kernel: bf16 engines run the dilated convs inside kair_conv3x3_dil's contract (IRCNN's 64 -> 64 layers,
+        forward and input gradient) on that kernel; False, like every other dilated conv, on the dilated im2col
+        operand of kair_gemm_nt (H.im2col(..., dil=d)).  Layers without dilation do not read it."""
         super().__init__(net, compute_dtype)
         self.residual = residual
+        self.dil_kernel = bool(dil_kernel)
         mods = self._conv_modules(net)
         self.device = mods[0].weight.device
         layers, i = [], 0
         while i < len(mods):
             conv = mods[i]
-            if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1):
-                raise NotImplementedError("kair_amd DnCNN: 3x3 / stride 1 / pad 1 convs only")
+            if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (3, 3) or conv.stride != (1, 1):
+                raise NotImplementedError("kair_amd DnCNN: 3x3 / stride 1 convs only")
+            d = conv.dilation[0]
+            if conv.dilation != (d, d) or conv.padding != (d, d) or not 1 <= d <= 4:
+                raise NotImplementedError("kair_amd DnCNN: padding == dilation == (d, d) with d in 1..4 only (got padding "
+                                          f"{conv.padding}, dilation {conv.dilation})")
             i += 1
             bn, act, slope = None, 0, 0.0
             if i < len(mods) and isinstance(mods[i], nn.BatchNorm2d):
@@ -55,7 +64,8 @@ class DnCNNEngine(ConvEngineBase):
         for li, (conv, bn, act, slope) in enumerate(layers):
             cop = self.Cout_p if li == len(layers) - 1 else conv.out_channels
             cip = self.Cin_p if li == 0 else conv.in_channels
-            self.layers.append((_Conv(self, conv, cop, cip, need_dgrad=li > 0), bn, act, slope))
+            self.layers.append((_Conv(self, conv, cop, cip, need_dgrad=li > 0, dil=conv.dilation[0],
+                                      dil_kernel=self.dil_kernel and li > 0), bn, act, slope))
 
     def convs(self):
         return [c for c, _, _, _ in self.layers]
@@ -116,6 +126,16 @@ class DnCNNEngine(ConvEngineBase):
         P["wg_ws"] = e(self.wgrad_ws_size(shapes))
         return P
 
+    def _conv_fwd(self, P, c, src, ldsrc, Cs, out, bias, act=H.ACT_NONE, slope=0.0):
+        """A body conv's forward product into the rows `out`: kair_conv3x3_dil where the layer is packed for it, else
+        the implicit GEMM over the (dilated) im2col operand."""
+        if c.dil_fast:
+            H.conv3x3_dil(src, ldsrc, c.dil, False, c.Wk15, 15, bias, out, P["B"], P["H"], P["W"], Cs, c.Cop, act=act,
+                          slope=slope)
+        else:
+            self._nt(H.im2col(src, P["H"], P["W"], Cs, ld=ldsrc, dil=c.dil), c.fwd(),
+                     H.epilogue(out, bias=bias, act=act, slope=slope), P["M"], c.Cop, 9 * c.Cip)
+
     def forward(self, x, *cond):
         """cond: the network's extra forward inputs (FFDNet: sigma); the trainer's drop-path slot (None) otherwise."""
         B, _, h, w = x.shape
@@ -132,19 +152,18 @@ class DnCNNEngine(ConvEngineBase):
         for li, (c, bn, act, slope) in enumerate(self.layers[:-1]):
             a = P["a"][li]
             if bn is None:
-                self._nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(),
-                         H.epilogue(a, bias=c.bp, act=(H.ACT_RELU if act == 1 else H.ACT_LEAKY) if act else H.ACT_NONE,
-                                    slope=slope), M, nc, 9 * c.Cip)
+                self._conv_fwd(P, c, src, ldsrc, Cs, a, c.bp,
+                               (H.ACT_RELU if act == 1 else H.ACT_LEAKY) if act else H.ACT_NONE, slope)
             else:
                 z = P["z"][li]
-                self._nt(H.im2col(src, Hh, Ww, Cs, ld=ldsrc), c.fwd(), H.epilogue(z, bias=c.bp), M, nc, 9 * c.Cip)
+                self._conv_fwd(P, c, src, ldsrc, Cs, z, c.bp)
                 H.bn_fwd(z, nc, a, nc, M, nc, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
                          training, P["mean"][li], P["rstd"][li], act, slope, P["bn_ws"])
                 if training:
                     bn.num_batches_tracked.add_(1)
             src, ldsrc, Cs = a, nc, nc
         c = self.layers[-1][0]
-        self._nt(H.im2col(src, Hh, Ww, nc), c.fwd(), self._out_epilogue(P, c), M, c.Cop, 9 * nc)
+        self._nt(H.im2col(src, Hh, Ww, nc, dil=c.dil), c.fwd(), self._out_epilogue(P, c), M, c.Cop, 9 * nc)
         if self.residual:
             H.axpby(P["E"], x, 1.0, -1.0)     # x - model(x)
         return P["E"]
@@ -167,8 +186,8 @@ class DnCNNEngine(ConvEngineBase):
         H.act_grad_cast(P["dEf"], Co, None, 0, P["dn"], Co, M, Co, 0, 0.0, -1.0 if self.residual else 1.0)
         c = self.layers[-1][0]
         G = P["G"]
-        self._nt(H.im2col(P["dn"], Hh, Ww, Co, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * Co)
-        self.conv_wgrad(P, c, P["dn"], Co, H.im2col(P["a"][-1], Hh, Ww, nc), M, grads)
+        self._nt(H.im2col(P["dn"], Hh, Ww, Co, flip=True, dil=c.dil), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * Co)
+        self.conv_wgrad(P, c, P["dn"], Co, H.im2col(P["a"][-1], Hh, Ww, nc, dil=c.dil), M, grads)
         for li in range(len(self.layers) - 2, -1, -1):
             c, bn, act, slope = self.layers[li]
             a, dz = P["a"][li], P["dz"]
@@ -182,10 +201,21 @@ class DnCNNEngine(ConvEngineBase):
             else:
                 bs = self.gate_cast(P, G, nc, a, nc, dz, nc, M, nc, act, slope)
             if li > 0:
-                self._nt(H.im2col(dz, Hh, Ww, nc, flip=True), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * nc)
-                self.conv_wgrad(P, c, dz, nc, H.im2col(P["a"][li - 1], Hh, Ww, nc), M, grads, *bs)
+                if c.dil_fast:   # the input gradient on the flipped taps, fp32 rows for gate_cast
+                    H.conv3x3_dil(dz, nc, c.dil, True, c.Wk16, 16, None, G, P["B"], Hh, Ww, nc, nc)
+                else:
+                    self._nt(H.im2col(dz, Hh, Ww, nc, flip=True, dil=c.dil), H.rows(c.Wd), H.epilogue(G), M, nc, 9 * nc)
+                self.conv_wgrad(P, c, dz, nc, H.im2col(P["a"][li - 1], Hh, Ww, nc, dil=c.dil), M, grads, *bs)
             else:
-                self.conv_wgrad(P, c, dz, nc, H.im2col(P["xin"], Hh, Ww, self.Cin_p), M, grads, *bs)
+                self.conv_wgrad(P, c, dz, nc, H.im2col(P["xin"], Hh, Ww, self.Cin_p, dil=c.dil), M, grads, *bs)
+
+
+class IRCNNEngine(DnCNNEngine):
+    """IRCNN (network_dncnn.IRCNN): DnCNN's layer loop with a dilation per conv, no BatchNorm, out = x - model(x)."""
+
+    def grad_segments(self):
+        """One gradient segment: 0.19 M parameters are one all-reduce bucket."""
+        return [list(self.net_ref().parameters())]
 
 
 class FFDNetEngine(DnCNNEngine):

@@ -4,6 +4,9 @@ Image Restoration with Deep Denoiser Prior"; the reference's main_dpir_deblur.py
 The reference scripts were not available when this was written: the loop is restated from memory of the published
 method, and tests/test_dpir_cpu.py / tests/test_dpir_gpu.py pin what it computes.
 
+With denoiser="ircnn" the prior step is the IRCNN model bank instead (network_dncnn.IRCNN; utils_model.IRCNNBank picks
+the entry of sigma_i), without a noise-map channel.
+
     x_0 = L (sf 1) or the bicubic x sf of L
     for i < iter_num:   x <- argmin_z ||(k (*) z)[::sf, ::sf] - L||^2 + rho_i ||z - x||^2   (utils_sisr.DataStep, HIP)
                         x <- DRUNet(cat(x, sigma_i map))                                    (x8: under augmentation i % 8)
@@ -43,8 +46,11 @@ def dpir_restore(net, L, k, sf=1, noise_level_img=0.0, iter_num=8, modelSigma1=4
 
     net: the DRUNet (in_nc = C + 1), on L's device; k: [B, 1, kh, kw] or one kernel for all images;
     noise_level_img: L's noise level, already divided by 255; x8: iteration i runs the denoiser under augmentation
-    mode i % 8; x0: the starting point instead of L / its bicubic upscale; denoiser: any callable [B, C + 1, H, W] ->
-    [B, C, H, W] instead of the network (then net may be None); split_min_size: run the network by
+    mode i % 8; x0: the starting point instead of L / its bicubic upscale; denoiser: None or "drunet" (the network), any
+    callable [B, C + 1, H, W] -> [B, C, H, W] instead of the network (then net may be None), or "ircnn": net is a
+    utils_model.IRCNNBank and iteration i's prior step is net.select(sigma_i * 255)(x), the IRCNN entry of that noise
+    level on the whole image, with no noise-map channel (the original plug-and-play prior DRUNet supersedes; data step,
+    schedule and x8 handling are the same); split_min_size: run the network by
     utils_model.test_mode's recursive 4-way split (mode 2) with this min_size instead of whole (mode 1).  Device
     tensors take the HIP data step (utils_sisr.DataStep), CPU tensors torch.fft in L's dtype (HostDataStep); nothing
     inside the loop reads a device value back."""
@@ -53,7 +59,16 @@ def dpir_restore(net, L, k, sf=1, noise_level_img=0.0, iter_num=8, modelSigma1=4
     sf = int(sf)
     modelSigma2 = max(0.255, 255.0 * noise_level_img)
     rhos, sigmas = utils_pnp.get_rho_sigma(max(0.255 / 255.0, noise_level_img), iter_num, modelSigma1, modelSigma2, w)
-    if denoiser is None:
+    ircnn = isinstance(denoiser, str) and denoiser == "ircnn"
+    if isinstance(denoiser, str):
+        if denoiser not in ("drunet", "ircnn"):
+            raise ValueError(f"dpir_restore: denoiser {denoiser!r} is neither 'drunet', 'ircnn' nor a callable")
+        denoiser = None
+    if ircnn:
+        if not hasattr(net, "select"):
+            raise ValueError("dpir_restore: denoiser='ircnn' takes a utils_model.IRCNNBank as net")
+        net.net.eval()
+    elif denoiser is None:
         if net is None:
             raise ValueError("dpir_restore: a network or a denoiser")
         net.eval()
@@ -74,6 +89,9 @@ def dpir_restore(net, L, k, sf=1, noise_level_img=0.0, iter_num=8, modelSigma1=4
             x = data.solve(x, rho_t[i:i + 1])
             mode = i % 8 if x8 else 0
             x = util.augment_img_tensor4(x, mode)
+            if ircnn:
+                x = _unaugment(net.select(float(sigmas[i]) * 255.0)(x.contiguous()), mode).to(L.dtype)
+                continue
             noise_map = x.new_full((B, 1) + tuple(x.shape[-2:]), float(sigmas[i]))
             x = denoiser(torch.cat((x, noise_map), dim=1))
             x = _unaugment(x, mode).to(L.dtype)
@@ -120,6 +138,8 @@ def main(argv=None):
                     help="the inputs are ground truth: degrade them (blur, downsample, noise) and report PSNR")
     ap.add_argument("--compute_dtype", choices=["fp32", "fp32x3", "bf16"], default="fp32")
     ap.add_argument("--split_min_size", type=int, default=None)
+    ap.add_argument("--denoiser", choices=["drunet", "ircnn"], default="drunet",
+                    help="the prior: a DRUNet checkpoint, or an IRCNN model bank (ircnn_gray.pth / ircnn_color.pth)")
     a = ap.parse_args(argv)
     if a.task == "deblur" and a.sf not in (None, 1):
         raise SystemExit("--task deblur has no scale factor")
@@ -129,8 +149,14 @@ def main(argv=None):
     out_dir = a.out or f"{a.input.rstrip(os.sep)}_dpir_{a.task}"
     os.makedirs(out_dir, exist_ok=True)
     dev = torch.device("cuda")
-    net = load_drunet(a.model_path, a.compute_dtype, dev)
-    n_channels = net.m_head.weight.shape[1] - 1
+    if a.denoiser == "ircnn":
+        from .main_test_ircnn_denoiser import load_ircnn
+        from .utils.utils_model import load_ircnn_bank
+        n_channels = next(iter(load_ircnn_bank(a.model_path).values()))["model.0.weight"].shape[1]
+        net = load_ircnn(a.model_path, n_channels, a.compute_dtype, dev)
+    else:
+        net = load_drunet(a.model_path, a.compute_dtype, dev)
+        n_channels = net.m_head.weight.shape[1] - 1
     k = load_kernel(a.kernel).to(dev)
     results, metrics = [], []
     for idx, path in enumerate(util.get_image_paths(a.input)):
@@ -142,7 +168,7 @@ def main(argv=None):
         else:
             L = img
         E = dpir_restore(net, L, k, sf=sf, noise_level_img=sigma, iter_num=iter_num, x8=a.x8,
-                         split_min_size=a.split_min_size)
+                         split_min_size=a.split_min_size, denoiser=a.denoiser if a.denoiser == "ircnn" else None)
         metrics.append(util.tensor_metrics(E, H, border=sf, ssim=False)[0, 0] if H is not None else None)
         name = os.path.splitext(os.path.basename(path))[0]
         util.imsave(util.tensor2uint(E), os.path.join(out_dir, f"{name}_dpir_{a.task}_x{sf}.png"))

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ..engine.base import ConvNetFunction
-from ..engine.dncnn_engine import DnCNNEngine
+from ..engine.dncnn_engine import DnCNNEngine, IRCNNEngine
 
 
 def _act(a, slope=0.2):
@@ -82,6 +82,42 @@ class DnCNN(_Base):
 
     def __init__(self, in_nc=1, out_nc=1, nc=64, nb=17, act_mode="BR", compute_dtype="fp32"):
         super().__init__(in_nc, out_nc, nc, nb, act_mode, compute_dtype)
+
+
+IRCNN_DILATIONS = (1, 2, 3, 4, 3, 2, 1)
+
+
+class IRCNN(_Base):
+    """IRCNN (upstream cszn/KAIR network_dncnn.py, restated; the sources are not in this tree): seven 3x3 convs with
+    bias, dilation = padding = 1, 2, 3, 4, 3, 2, 1, ReLU between them, no BatchNorm; out = x - model(x).  state_dict
+    keys model.{0,2,...,12}.{weight,bias}.  The dilated 64 -> 64 layers run on kair_conv3x3_dil under bf16
+    (set_dil_kernel(False): on the dilated im2col operand of kair_gemm_nt, as fp32 does)."""
+
+    def __init__(self, in_nc=1, out_nc=1, nc=64, compute_dtype="fp32"):
+        nn.Module.__init__(self)
+        mods = []
+        for li, d in enumerate(IRCNN_DILATIONS):
+            ci = in_nc if li == 0 else nc
+            co = out_nc if li == len(IRCNN_DILATIONS) - 1 else nc
+            mods.append(nn.Conv2d(ci, co, 3, 1, padding=d, dilation=d, bias=True))
+            if li < len(IRCNN_DILATIONS) - 1:
+                mods.append(nn.ReLU(inplace=True))
+        self.model = nn.Sequential(*mods)
+        self.compute_dtype = compute_dtype
+        self.dil_kernel = True
+        self._engine = None
+
+    def engine(self):
+        if self._engine is None or self._engine.net_ref() is not self:
+            self._engine = IRCNNEngine(self, self.compute_dtype, residual=True, dil_kernel=self.dil_kernel)
+        return self._engine
+
+    def set_dil_kernel(self, on):
+        """bf16: run the dilated 64 -> 64 convs on kair_conv3x3_dil (True, the default) or on the generic dilated
+        im2col GEMM (False) -- for A/B runs and tests."""
+        self.dil_kernel = bool(on)
+        self._engine = None
+        return self
 
 
 class FDnCNN(_Base):

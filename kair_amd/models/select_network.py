@@ -2,8 +2,8 @@
 
 `opt['netG']['net_type']` selects the network; constructor kwargs are taken from opt['netG'] under
 the reference's key names, and init_weights() runs when opt['is_train'] (select_network.py:268-272).
-Networks on the MI355X path: swinir, dncnn, fdncnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet, msrresnet0, imdn, dpsr,
-scunet.
+Networks on the MI355X path: swinir, dncnn, fdncnn, ircnn, ffdnet, srmd, rrdb, rrdbnet, usrnet, drunet, msrresnet0, imdn,
+dpsr, scunet.
 Everything else the reference's define_G knows (msrresnet1 -- the bilinear-base MSRResNet kept upstream for the original
 checkpoints --, vrt, rvrt, ...) is out of scope for this build and raises NotImplementedError naming
 the type.
@@ -16,7 +16,7 @@ from torch.nn import init
 logger = logging.getLogger("kair_amd")
 
 _ON_PATH = ("swinir", "dncnn", "fdncnn", "ffdnet", "srmd", "rrdb", "rrdbnet", "usrnet", "drunet", "msrresnet0", "imdn",
-            "dpsr", "scunet")
+            "dpsr", "scunet", "ircnn")
 
 
 def define_G(opt):
@@ -35,6 +35,9 @@ def define_G(opt):
         cls = DnCNN if t == "dncnn" else FDnCNN
         net = cls(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], act_mode=o["act_mode"],
                   **ek)
+    elif t == "ircnn":   # seven dilated 3x3 convs (dilation 1, 2, 3, 4, 3, 2, 1), trained by ModelPlain ('plain')
+        from .network_dncnn import IRCNN
+        net = IRCNN(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], **ek)
     elif t == "ffdnet":   # two inputs: net(x, sigma), trained by ModelPlain2 ('plain2')
         from .network_ffdnet import FFDNet
         net = FFDNet(in_nc=o["in_nc"], out_nc=o["out_nc"], nc=o["nc"], nb=o["nb"], act_mode=o["act_mode"], **ek)

@@ -123,3 +123,86 @@ def test_tiled(model, L, tile=None, tile_overlap=32, sf=1, window_size=8, tile_b
 def find_last_checkpoint(save_dir, net_type="G", pretrained_path=None):
     from .utils_option import find_last_checkpoint as f
     return f(save_dir, net_type, pretrained_path)
+
+
+# ---- the IRCNN model bank (upstream ircnn_gray.pth / ircnn_color.pth: 25 state dicts, one per noise level) -------------
+IRCNN_LEVELS = 25
+
+
+def ircnn_index(sigma_255):
+    """The bank entry for a noise level on the 0-255 scale: min(24, max(0, ceil(sigma / 2) - 1)) -- entry i was trained
+    for sigma = 2 (i + 1)."""
+    return min(IRCNN_LEVELS - 1, max(0, int(math.ceil(float(sigma_255) / 2.0)) - 1))
+
+
+def _ircnn_check(sd, what):
+    """in_nc of an IRCNN state dict; ValueError naming the first key or shape that is wrong."""
+    from ..models.network_dncnn import IRCNN_DILATIONS
+    if not isinstance(sd, dict) or "model.0.weight" not in sd:
+        raise ValueError(f"{what}: not an IRCNN state dict (no 'model.0.weight')")
+    w0 = sd["model.0.weight"]
+    if w0.dim() != 4:
+        raise ValueError(f"{what}: model.0.weight has shape {tuple(w0.shape)}, not [nc, in_nc, 3, 3]")
+    nc, in_nc = w0.shape[:2]
+    want, last = {}, len(IRCNN_DILATIONS) - 1
+    for li in range(len(IRCNN_DILATIONS)):
+        co, ci = (in_nc if li == last else nc), (in_nc if li == 0 else nc)
+        want[f"model.{2 * li}.weight"], want[f"model.{2 * li}.bias"] = (co, ci, 3, 3), (co,)
+    missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
+    if missing or extra:
+        raise ValueError(f"{what}: IRCNN keys are model.{{0,2,...,12}}.{{weight,bias}}; missing {missing}, unexpected {extra}")
+    for key, shape in want.items():
+        if tuple(sd[key].shape) != shape:
+            raise ValueError(f"{what}: {key} has shape {tuple(sd[key].shape)}, expected {shape}")
+    return in_nc, nc
+
+
+def load_ircnn_bank(path):
+    """{index: state_dict} from a torch-saved IRCNN bank: the upstream layout, a dict of state dicts keyed "0" ... "24"
+    (one per noise level), or a single state dict (a one-level bank, index 0).  `path` may also be the loaded object.
+    Keys and shapes are checked against network_dncnn.IRCNN (all entries of one width); ValueError names what is wrong."""
+    obj = torch.load(path, map_location="cpu") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
+    if not isinstance(obj, dict) or not obj:
+        raise ValueError("IRCNN bank: a dict of state dicts keyed '0' ... '24', or one state dict")
+    if all(torch.is_tensor(v) for v in obj.values()):
+        _ircnn_check(obj, "IRCNN bank (single state dict)")
+        return {0: dict(obj)}
+    bank = {}
+    for key, sd in obj.items():
+        if not str(key).isdigit() or not 0 <= int(key) < IRCNN_LEVELS:
+            raise ValueError(f"IRCNN bank: entry key {key!r} is not one of '0' ... '{IRCNN_LEVELS - 1}'")
+        bank[int(key)] = sd
+    shapes = {_ircnn_check(sd, f"IRCNN bank entry {i!r}") for i, sd in sorted(bank.items())}
+    if len(shapes) != 1:
+        raise ValueError(f"IRCNN bank: entries of different widths (in_nc, nc): {sorted(shapes)}")
+    return bank
+
+
+class IRCNNBank:
+    """One IRCNN network and its bank: select(sigma_255) loads entry ircnn_index(sigma_255) into the network when the
+    index changes (load_state_dict copies in place, which moves the parameters' versions: the engine repacks its
+    weight forms on the next forward).  A bank with fewer than 25 entries serves a level from its nearest entry at or
+    below the index (a one-level bank: always entry 0).  The entries are moved to the network's device once."""
+
+    def __init__(self, net, bank):
+        if not bank:
+            raise ValueError("IRCNNBank: an empty bank")
+        dev = next(net.parameters()).device
+        self.net = net
+        self.bank = {int(i): {k: v.to(dev) for k, v in sd.items()} for i, sd in bank.items()}
+        self.current = None
+
+    def index(self, sigma_255):
+        want = ircnn_index(sigma_255)
+        below = [i for i in self.bank if i <= want]
+        return max(below) if below else min(self.bank)
+
+    def select(self, sigma_255):
+        i = self.index(sigma_255)
+        if i != self.current:
+            self.net.load_state_dict(self.bank[i], strict=True)
+            self.current = i
+        return self.net
+
+    def __call__(self, x, sigma_255):
+        return self.select(sigma_255)(x)
